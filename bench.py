@@ -20,11 +20,22 @@ by `bench.py --gpus N` itself (spawn_ranks: N fresh rank processes, rendezvous o
 GOPs sharded by rank, no data-path collective; RCCL is used only after timing (max-time
 all_reduce, per-rank stats all_gather, bitstreams gathered to rank 0).
 
-After timing, every rank checks its own first GOP's frame 1 against the oracle (BASELINE.md §3's
-parity block: symbol / index mismatch counts, dPSNR, dbpp_est and a byte-exact stream check
-against the C oracle coder), gathered to rank 0 as `quality.parity_by_rank`; rank 0 then times
-the oracle on the host cores (--cpu-baseline quick|full|none) at every N, so every line, single-
-or multi-GPU, carries its own CPU baseline and parity.
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the
+streamed GOPs' overflow probes, --dump-outputs if given, and the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, the configuration and the shards).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (bitstreams, decoder
+recons, encoder SSEs, encoder recons) as DIR/<name>.npy, see GpuGopJob.outputs: the recons and the
+bitstream words as a fixed seeded sample, at most 64 MB in all. The inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
+
+--full adds everything else, after timing: the serial roofline pass (HIP events around every
+launch), the decoder bit-exactness check and the bitstream gather (`quality`), every rank's check
+of its own first GOP's frame 1 against the oracle (BASELINE.md §3's parity block: symbol / index
+mismatch counts, dPSNR, dbpp_est and a byte-exact stream check against the C oracle coder),
+gathered to rank 0 as `quality.parity_by_rank`, the reference-comparable batch-1 figures, and the
+oracle timed on the host cores by rank 0 (--cpu-baseline quick|full|none) at every N, so every
+--full line, single- or multi-GPU, carries its own CPU baseline and parity.
 """
 from __future__ import annotations
 
@@ -60,6 +71,11 @@ ONE_THREAD_1080_BUDGET_S = 240.0  # cap on the CPU leg's 1-thread 1080p run (BAS
 # the north star's PSNR tolerance
 SYMBOL_FLIP_BOUND = 1.56e-5
 DPSNR_BOUND_DB = 1e-4
+# --dump-outputs: sample seed, and the bytes the recon samples / the bitstream word samples of all
+# ranks may take (float32 / float64 elements; the small per-frame arrays come on top, < 64 MB in all)
+DUMP_SEED = 20261015
+DUMP_RECON_BYTES = 40 << 20
+DUMP_WORDS_BYTES = 8 << 20
 
 
 def parity_rank_cap(args, world):
@@ -442,10 +458,15 @@ class GpuGopJob:
             if args.views < world:
                 raise SystemExit(f"--views {args.views} < world size {world}: a rank would have no view")
             mine = fdist.shard_views(args.views, rank, world)
-            gops = [make_gop(args.height, args.width, args.gop, gop_seed(0, v)) for v in mine]
+            seeds = [gop_seed(0, v) for v in mine]
         else:
             mine = fdist.shard_gops(world * args.gops_per_gpu, rank, world)  # GOP g -> rank g % world
-            gops = [make_gop(args.height, args.width, args.gop, gop_seed(g)) for g in mine]
+            seeds = [gop_seed(g) for g in mine]
+        # every GOP has its own seeded generator, so the GOPs are made side by side on the host
+        # cores (numpy releases the GIL in the sampling and the noise; ~4 s per 1080p GOP-12 each)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max(1, min(len(seeds), cpu_cores(), 16))) as ex:
+            gops = list(ex.map(lambda sd: make_gop(args.height, args.width, args.gop, sd), seeds))
         self.shard = mine  # GOP (or view) ids this rank codes
         self.gops_np = gops
         self.units = len(gops)
@@ -457,11 +478,10 @@ class GpuGopJob:
             from fastvideocodec_amd.tree_gop import encode_decode_tree_gop
             # streamed like the linear GOP: no per-step host wait, overflow probes resolved in
             # after_timing (gop.check_overflow); past 31 P-frames the 62-frame binary tree
-            encode_decode_tree_gop(self.model, self.frames, overlap=not self.args.serial, join=False,
-                                   extend=True)
-            return
+            return encode_decode_tree_gop(self.model, self.frames, overlap=not self.args.serial, join=False,
+                                          extend=True)
         from fastvideocodec_amd.gop import encode_decode_gop
-        encode_decode_gop(self.model, self.frames, overlap=not self.args.serial, join=False)
+        return encode_decode_gop(self.model, self.frames, overlap=not self.args.serial, join=False)
 
     def sync(self):
         torch.cuda.synchronize()
@@ -470,13 +490,53 @@ class GpuGopJob:
         from fastvideocodec_amd.tree_gop import coding_layers
         return coding_layers(self.args.gop - 1, extend=True)
 
+    def resolve_overflow(self):
+        """The streamed GOPs' overflow probes (the host wait the timed steps leave out)."""
+        from fastvideocodec_amd import gop
+        gop.check_overflow(self.model)  # raises if a timed GOP left the split-precision range
+
+    def outputs(self, last, world=1):
+        """What the timed path returned in its last step (gop.encode_decode_gop / tree_gop.
+        encode_decode_tree_gop: bitstreams, decoder recons, encoder SSEs, encoder recons) as host
+        arrays for --dump-outputs, one row per bitstream / recon in the path's own order (P-frame
+        1.. for the sequential GOP; tree layers for the bitstreams and SSEs of --tree):
+          sample_index            flat indexes into a [G, 3, Hp, Wp] recon the samples are taken at
+                                  (fixed, seeded; every element where the recons fit the budget)
+          decoded_sample          decoder recons at sample_index, float32
+          encoder_recon_sample    encoder recons at sample_index, float32
+          sse                     the encoder's SSE sums (recon, warp, prediction, clipped), float64
+          bitstream_nbytes        bytes of each bitstream (its mv + z + feature streams)
+          bitstream_words_sample  32-bit words of each bitstream (mv, z, feature streams in that
+                                  order) at fixed seeded fractions of its length, float64"""
+        bss, dec, sses, enc = last
+        if isinstance(dec, dict):
+            dec, enc = [dec[t] for t in sorted(dec)], [enc[t] for t in sorted(enc)]
+        rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        numel = dec[0].numel()
+        n = min(numel, DUMP_RECON_BYTES // world // (2 * 4 * len(dec)))
+        idx = np.arange(numel) if n == numel else np.sort(rng.integers(0, numel, n))
+        frac = np.sort(rng.random(DUMP_WORDS_BYTES // world // (8 * len(bss))))
+        didx, dfrac = torch.from_numpy(idx).to(self.dev), torch.from_numpy(frac).to(self.dev)
+        take = lambda ts: np.stack([t.reshape(-1)[didx].float().cpu().numpy() for t in ts])  # noqa: E731
+        words, nbytes = [], []
+        for bs in bss:
+            bs.check()
+            w = torch.cat([p.packed[: int(p.pack_off[-1])] for p in (bs.mv, bs.z, bs.feature)])
+            pos = (dfrac * w.numel()).long().clamp_(max=w.numel() - 1)
+            words.append((w[pos].long() & 0xFFFFFFFF).double().cpu().numpy())
+            nbytes.append(4.0 * w.numel())
+        return {"sample_index": idx.astype(np.float64), "decoded_sample": take(dec),
+                "encoder_recon_sample": take(enc),
+                "sse": np.stack([s.double().cpu().numpy() for s in sses]),
+                "bitstream_nbytes": np.asarray(nbytes, np.float64), "bitstream_words_sample": np.stack(words)}
+
     def after_timing(self):
         """Roofline pass: one serial GOP (single stream) with HIP events around every launch on
         the launching stream (in the overlapped timed region concurrent kernels would be charged
         to each other's event windows); plus the streamed GOPs' overflow probes."""
-        from fastvideocodec_amd import gop, profiling
+        from fastvideocodec_amd import profiling
         from fastvideocodec_amd.gop import encode_decode_gop
-        gop.check_overflow(self.model)  # raises if a timed GOP left the split-precision range
+        self.resolve_overflow()
         timer = profiling.KernelTimer()
         with timer:
             encode_decode_gop(self.model, self.frames, overlap=False)
@@ -534,9 +594,16 @@ class HostRehearsalJob:
 
     def step(self):
         time.sleep(0.005 * (1 + self.rank))
+        return self.shard
 
     def sync(self):
         pass
+
+    def resolve_overflow(self):
+        pass
+
+    def outputs(self, last, world=1):
+        return {"shard": np.asarray(last, np.float64)}
 
     def after_timing(self):
         return None
@@ -557,44 +624,60 @@ class HostRehearsalJob:
 
 
 def run_rank(job, args, rank, world, device):
-    """Warm-up, the timed region (barrier + device sync on both sides, max over ranks), then one
-    collective round after timing. Returns the result dict on rank 0, None elsewhere."""
+    """Warm-up, the timed region (barrier + device sync on both sides, max over ranks), the
+    outputs of the last timed step if --dump-outputs asks for them, then one collective round
+    after timing; with --full the roofline pass, the decoder check and the parity blocks before
+    it. Returns the result dict on rank 0, None elsewhere."""
+    full = getattr(args, "full", False)
+    dump = getattr(args, "dump_outputs", None)
     for _ in range(args.warmup):
         job.step()
     job.sync()
     if world > 1:
         dist.barrier()
     job.sync()
+    last = None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        job.step()
+    for i in range(args.steps):
+        if dump and i == args.steps - 1:
+            last = job.step()  # what a caller of the timed path receives, kept for the dump
+        else:
+            job.step()
     job.sync()
     if world > 1:
         dist.barrier()
     job.sync()
     dt = time.perf_counter() - t0
 
-    prof = job.after_timing()
-    ver = job.verify()
+    if not full:
+        job.resolve_overflow()  # with --full, after_timing does it
+    if dump:
+        os.makedirs(dump, exist_ok=True)
+        for name, arr in job.outputs(last, world).items():
+            np.save(os.path.join(dump, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+        last = None
+    prof = job.after_timing() if full else None
+    ver = job.verify() if full else None
     # every rank checks its own first unit against the oracle (host threads shared among the
     # node's ranks), before the collectives so the ranks do it concurrently
     par = coder = None
     cap = parity_rank_cap(args, world)
-    if getattr(args, "cpu_baseline", "none") != "none" and hasattr(job, "parity") and rank < cap:
+    if full and getattr(args, "cpu_baseline", "none") != "none" and hasattr(job, "parity") and rank < cap:
         par, coder = job.parity(max(1, cpu_cores() // cap))
-    pvec = fdist.gather_stats(parity_vector(par), device)
     dt_max = fdist.max_over_ranks(dt, device)
-    allst = fdist.gather_stats([1.0 if ver["bitexact"] else 0.0, float(ver["nbytes"]), ver["psnr"],
-                                float(job.units), float(ver["overflow_recomputes"])], device)
-    gathered = fdist.gather_bytes(ver["payload"], device, dst=0)
     shards = fdist.gather_bytes(json.dumps(list(getattr(job, "shard", []))).encode(), device, dst=0)
+    if full:
+        pvec = fdist.gather_stats(parity_vector(par), device)
+        allst = fdist.gather_stats([1.0 if ver["bitexact"] else 0.0, float(ver["nbytes"]), ver["psnr"],
+                                    float(job.units), float(ver["overflow_recomputes"])], device)
+        gathered = fdist.gather_bytes(ver["payload"], device, dst=0)
+        units = int(allst[:, 3].sum())
+    else:
+        units = int(fdist.gather_stats([float(job.units)], device).sum())
     if rank != 0:
         return None
-    units = int(allst[:, 3].sum())
     pframes_per_step = units * (args.gop - 1)
     value = args.steps * pframes_per_step / dt_max
-    bitexact_all = bool(np.all(allst[:, 0] == 1.0)) and sum(len(g) for g in gathered) == int(allst[:, 1].sum())
-    bytes_all = float(allst[:, 1].sum())
     enc_tf, dec_tf = tflop_per_pframe(job.Hp, job.Wp)
     res_label = f"{args.width}x{args.height} (padded {job.Wp}x{job.Hp})"
     tree_info = None
@@ -633,16 +716,20 @@ def run_rank(job, args, rank, world, device):
                    "by_rank": [json.loads(s.decode()) for s in shards]},
         "model_tflop_per_pframe": round(enc_tf + dec_tf, 3),
         "effective_tflops": round(value / world * (enc_tf + dec_tf), 2),
-        "quality": {"decoder_bitexact": bitexact_all,
-                    "bytes_per_pframe": round(bytes_all / pframes_per_step, 1),
-                    "bpp_actual": round(bytes_all * 8 / (pframes_per_step * job.Hp * job.Wp), 5),
-                    "psnr_db_mean": round(float(np.mean(allst[:, 2])), 4),
-                    "overflow_recomputes": int(allst[:, 4].sum()),
-                    "bitstreams_gathered_to_rank0_bytes": sum(len(g) for g in gathered),
-                    "note": "seeded (untrained) codec weights + synthetic GOP: PSNR/bpp are not rate-distortion "
-                            "figures; the coder's symbol statistics (and so its timing) are those of untrained "
-                            "weights (~5 bpp vs DVC's 0.137 bpp at lambda=1024)"},
     }
+    if full:
+        bitexact_all = bool(np.all(allst[:, 0] == 1.0)) and sum(len(g) for g in gathered) == int(allst[:, 1].sum())
+        bytes_all = float(allst[:, 1].sum())
+        result["quality"] = {
+            "decoder_bitexact": bitexact_all,
+            "bytes_per_pframe": round(bytes_all / pframes_per_step, 1),
+            "bpp_actual": round(bytes_all * 8 / (pframes_per_step * job.Hp * job.Wp), 5),
+            "psnr_db_mean": round(float(np.mean(allst[:, 2])), 4),
+            "overflow_recomputes": int(allst[:, 4].sum()),
+            "bitstreams_gathered_to_rank0_bytes": sum(len(g) for g in gathered),
+            "note": "seeded (untrained) codec weights + synthetic GOP: PSNR/bpp are not rate-distortion "
+                    "figures; the coder's symbol statistics (and so its timing) are those of untrained "
+                    "weights (~5 bpp vs DVC's 0.137 bpp at lambda=1024)"}
     if par is not None:
         by_rank = []
         for r, v in enumerate(pvec):
@@ -856,9 +943,18 @@ def parse_args(argv=None):
     ap.add_argument("--views", type=int, default=0,
                     help="BASELINE configs[4]: V camera views, one GOP stream each, view v -> rank v %% world "
                          "(replaces --gops-per-gpu; the reference's MCVC couples views, DVC views are independent)")
+    ap.add_argument("--full", action="store_true",
+                    help="after timing, also measure and check everything beside the headline figure: the "
+                         "serial roofline pass, decoder bit-exactness and the bitstream gather, oracle parity, "
+                         "the reference-comparable batch-1 figures and the CPU baseline (the options below "
+                         "that trim these act under --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (GpuGopJob.outputs: bitstream sizes and word "
+                         "samples, decoder / encoder recon samples, encoder SSEs) as DIR/<name>.npy, "
+                         "<name>_rank<r>.npy at N > 1; fixed seeded samples, < 64 MB in all")
     ap.add_argument("--cpu-baseline", choices=("quick", "full", "none"), default="full",
-                    help="CPU leg + parity block on rank 0 at N=1: full (default; BASELINE.md §3 protocol, "
-                         "~3 min), quick (~30 s), none")
+                    help="with --full, CPU leg + parity block on rank 0: full (default; BASELINE.md §3 "
+                         "protocol, ~3 min), quick (~30 s), none")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--no-ref-metrics", dest="ref_metrics", action="store_false",
                     help="skip the reference-comparable batch-1 figures (stage split, per-frame decode time, "
@@ -883,6 +979,12 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.no_cpu_baseline:
         args.cpu_baseline = "none"
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        for opt in ("breakdown", "strict_parity"):
+            if getattr(args, opt):
+                ap.error(f"--{opt.replace('_', '-')} needs --full (the pass it reports on runs there)")
     if args.gops_per_gpu is None:
         args.gops_per_gpu = 4 if args.tree else 16
     return args
@@ -966,10 +1068,10 @@ def main(argv=None):
     result = run_rank(job, args, rank, world, dev)
     if args.dry_run and rank == 0:
         result["data"] = "dry run: host rehearsal job, no GPU work (launcher / sharding / collectives only)"
-    if rank == 0 and not args.dry_run and args.ref_metrics:
+    if rank == 0 and args.full and not args.dry_run and args.ref_metrics:
         result["reference_comparable"] = reference_metrics(job.model, job.frames[0])
-    # the CPU leg on rank 0 at every N, after the timed region and the collectives
-    if rank == 0 and args.cpu_baseline != "none":
+    # --full: the CPU leg on rank 0 at every N, after the timed region and the collectives
+    if rank == 0 and args.full and args.cpu_baseline != "none":
         coder = result.pop("_coder", None)
         if args.dry_run:
             result["cpu_baseline"] = dry_cpu_baseline()

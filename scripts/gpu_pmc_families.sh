@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 TAG=${1:?tag}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-SERIAL="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-ref-metrics --serial $EXTRA"
+SERIAL="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-ref-metrics --serial $EXTRA"
 pass() {
   local name=$1; shift
   timeout -s KILL 420 rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -o run -- $SERIAL \

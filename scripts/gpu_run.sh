@@ -5,8 +5,8 @@
 #   tests            full -m gpu suite, one pytest process
 #   tests:EXPR       -m gpu tests selected by -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            default bench (CPU leg + parity block)        -> OUT/bench.json
-#   bench-fast       pipelined bench, no CPU leg, STEPS (default 6) -> OUT/bench_fast.json
+#   bench            bench.py --full (roofline, CPU leg + parity block) -> OUT/bench.json
+#   bench-fast       plain pipelined bench, STEPS (default 6)       -> OUT/bench_fast.json
 #   breakdown        serial bench with the per-geometry table on stderr
 #   prof             rocprofv3 --kernel-trace --stats of the serial bench
 #   pmc              FETCH_SIZE and WRITE_SIZE passes of the serial bench (one counter group a run)
@@ -17,7 +17,7 @@ TAG=${1:?tag}; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 STEPS=${STEPS:-6}
-SERIAL="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-ref-metrics --serial $EXTRA"
+SERIAL="python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-ref-metrics --serial $EXTRA"
 run() {  # run NAME SECONDS CMD...: log to OUT/NAME.log, stop the script on failure
   local name=$1 secs=$2; shift 2
   echo "[gpu_run] $name: $*"
@@ -33,7 +33,7 @@ for step in "$@"; do
     tests:*) run pytest_k 900 python -u -m pytest tests -m gpu -v --timeout 420 --timeout-method thread \
              -p no:cacheprovider -rP --tb=short -k "${step#tests:}" ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    bench) run bench 900 python -u bench.py --json-out $OUT/bench.json $EXTRA ;;
+    bench) run bench 900 python -u bench.py --full --json-out $OUT/bench.json $EXTRA ;;
     bench-fast) run bench_fast 600 python -u bench.py --steps $STEPS --warmup 2 --no-cpu-baseline --no-ref-metrics \
              --json-out $OUT/bench_fast.json $EXTRA ;;
     breakdown) run breakdown 600 $SERIAL --breakdown ;;

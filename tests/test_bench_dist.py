@@ -54,7 +54,7 @@ def _worker(rank, world, port, q):
     import bench
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        args = bench.parse_args(["--steps", "3", "--warmup", "1", "--gops-per-gpu", "2", "--height", "64",
+        args = bench.parse_args(["--full", "--steps", "3", "--warmup", "1", "--gops-per-gpu", "2", "--height", "64",
                                  "--width", "128", "--gop", "5"])
         job = StandInJob(rank, world, args.gops_per_gpu)
         res = bench.run_rank(job, args, rank, world, None)
@@ -90,12 +90,41 @@ def test_bench_run_rank_gloo_ws2():
     assert res["metric"].startswith("128x64 ")       # non-1080p runs say so in the metric
 
 
-def _run_bench_cli(argv, tmp_path):
+def _run_bench_cli(argv, tmp_path, full=True):
     import bench
     out = tmp_path / "line.json"
-    rc = bench.main(argv + ["--dry-run", "--json-out", str(out)])
+    rc = bench.main(argv + (["--full"] if full else []) + ["--dry-run", "--json-out", str(out)])
     assert rc == 0
     return json.loads(out.read_text())
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline fields and none of the extra legs (quality,
+    parity, CPU baseline, roofline); --steps is the number of timed steps ms_per_step averages
+    over; --dump-outputs writes every rank's last-step outputs as float .npy files."""
+    d = tmp_path / "dump"
+    res = _run_bench_cli(["--gpus", "2", "--steps", "3", "--warmup", "1", "--gops-per-gpu", "2", "--height", "64",
+                          "--width", "128", "--gop", "4", "--dump-outputs", str(d)], tmp_path, full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res
+    assert res["steps"] == 3 and res["n_gpus"] == 2 and res["unit"] == "P-frames/s"
+    assert not {"quality", "cpu_baseline", "roofline", "reference_comparable", "hbm_kernels"} & set(res)
+    assert res["shards"]["by_rank"] == [[0, 2], [1, 3]]
+    # 4 GOPs x 3 P-frames per step; rank 1's 10 ms steps bound each of the 3 timed steps
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - 4 * 3) < 1e-2 * 4 * 3 and res["ms_per_step"] >= 10 * 0.9
+    assert sorted(p.name for p in d.iterdir()) == ["shard_rank0.npy", "shard_rank1.npy"]
+    a = np.load(d / "shard_rank1.npy")
+    assert a.dtype == np.float64 and a.tolist() == [1.0, 3.0]
+
+
+def test_bench_full_only_options_need_full():
+    """--breakdown and --strict-parity report on passes that run under --full only."""
+    import pytest
+    import bench
+    for opt in ("--breakdown", "--strict-parity"):
+        with pytest.raises(SystemExit):
+            bench.parse_args([opt])
+        assert bench.parse_args([opt, "--full"]).full
 
 
 def test_bench_gpus2_spawns_two_ranks(tmp_path):

@@ -61,10 +61,73 @@ def test_run_rank_default_config(dev):
     fields and the decoder bit-exactness check."""
     import bench
 
-    job = bench.GpuGopJob(_args(steps=2, warmup=1), 0, 1, dev)
+    job = bench.GpuGopJob(_args(steps=2, warmup=1, full=True), 0, 1, dev)
     res = bench.run_rank(job, job.args, 0, 1, dev)
     assert res["n_gpus"] == 1 and res["steps"] == 2 and res["value"] > 0
     assert res["quality"]["decoder_bitexact"] is True
+
+
+def test_run_rank_plain_dumps_last_step_outputs(dev, tmp_path, monkeypatch):
+    """A plain run (no --full): headline fields only, and --dump-outputs writes what the last timed
+    step returned: float arrays that equal the same GOPs coded by a joined call, the same from run
+    to run, decoder samples == encoder samples. With a small recon budget the sample is a fixed
+    subset of the same values."""
+    import bench
+    from fastvideocodec_amd.gop import encode_decode_gop
+
+    def run(d):
+        job = bench.GpuGopJob(_args(steps=2, warmup=1, dump_outputs=str(d)), 0, 1, dev)
+        res = bench.run_rank(job, job.args, 0, 1, dev)
+        return job, res, {p.stem: np.load(p) for p in sorted(d.iterdir())}
+
+    job, res, a = run(tmp_path / "a")
+    assert res["steps"] == 2 and res["value"] > 0 and res["ms_per_step"] > 0
+    assert not {"quality", "roofline", "hbm_kernels", "cpu_baseline"} & set(res)
+    assert sorted(a) == ["bitstream_nbytes", "bitstream_words_sample", "decoded_sample", "encoder_recon_sample",
+                         "sample_index", "sse"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    bss, dec, sses, enc = encode_decode_gop(job.model, job.frames, check=True, overlap=True)
+    torch.cuda.synchronize()
+    n = dec[0].numel()
+    assert a["sample_index"].tolist() == list(range(n)) and a["decoded_sample"].shape == (2, n)
+    for t in range(2):
+        assert np.array_equal(a["decoded_sample"][t], dec[t].reshape(-1).cpu().numpy())
+        assert np.array_equal(a["encoder_recon_sample"][t], a["decoded_sample"][t])
+        assert np.array_equal(a["sse"][t], sses[t].cpu().numpy())
+        assert a["bitstream_nbytes"][t] == bss[t].nbytes()
+        w = np.concatenate([np.frombuffer(b"".join(p.to_bytes_list()), "<u4") for p in (bss[t].mv, bss[t].z,
+                                                                                       bss[t].feature)])
+        assert np.isin(a["bitstream_words_sample"][t], w.astype(np.float64)).all()
+
+    _, _, b = run(tmp_path / "b")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    monkeypatch.setattr(bench, "DUMP_RECON_BYTES", 2 * 4 * 2 * 1000)  # 1000 samples per recon
+    _, _, c = run(tmp_path / "c")
+    idx = c["sample_index"].astype(np.int64)
+    assert idx.shape == (1000,) and (np.diff(idx) >= 0).all() and idx.max() < n
+    assert np.array_equal(c["decoded_sample"], a["decoded_sample"][:, idx])
+
+
+def test_run_rank_tree_dumps_last_step_outputs(dev, tmp_path):
+    """--tree --dump-outputs: recons in P-frame order (one row per frame), bitstreams and SSEs one
+    row per tree layer; equal to the joined tree call on the same GOPs."""
+    import bench
+    from fastvideocodec_amd.tree_gop import coding_layers, encode_decode_tree_gop
+
+    job = bench.GpuGopJob(_args(tree=True, gop=6, steps=1, dump_outputs=str(tmp_path)), 0, 1, dev)
+    res = bench.run_rank(job, job.args, 0, 1, dev)
+    a = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    nlay = len(coding_layers(5, extend=True))
+    assert res["config"]["tree"]["depth"] == nlay
+    assert a["decoded_sample"].shape[0] == 5 and a["sse"].shape == (nlay, 4) and a["bitstream_nbytes"].shape == (nlay,)
+    bss, dec, sses, enc = encode_decode_tree_gop(job.model, job.frames, check=True, extend=True)
+    torch.cuda.synchronize()
+    for row, t in enumerate(sorted(dec)):
+        assert np.array_equal(a["decoded_sample"][row], dec[t].reshape(-1).cpu().numpy())
+        assert np.array_equal(a["encoder_recon_sample"][row], enc[t].reshape(-1).cpu().numpy())
+    assert a["bitstream_nbytes"].tolist() == [float(b.nbytes()) for b in bss]
+    assert np.array_equal(a["sse"], np.stack([s.cpu().numpy() for s in sses]))
 
 
 def test_4k_gop_batch_split_pipeline(dev):
