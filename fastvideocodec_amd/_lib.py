@@ -111,6 +111,10 @@ _SIGS = {
     "fvc_torchac_max_bytes": (c_size_t, [ctypes.c_int64]),
     "fvc_torchac_encode": (c_int, [vp, vp, ctypes.c_int64, vp, c_size_t, vp]),
     "fvc_torchac_decode": (c_int, [vp, c_int, vp, ctypes.c_int64, ctypes.c_int64, vp, c_size_t, vp]),
+    "fvc_pixfmt_coeffs": (c_int, [c_int, c_int, vp, vp, vp]),
+    "fvc_yuv420_to_rgb_pad": (c_int, [vp, vp, vp, vp] + [c_int] * 7 + [vp]),
+    "fvc_rgb_to_yuv420_crop": (c_int, [vp, vp, vp, vp] + [c_int] * 7 + [vp]),
+    "fvc_sse_u8": (c_int, [vp, vp, c_size_t, vp, vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -17,7 +17,8 @@ files it deletes (models.py:412-429). Layout (little-endian):
 
 The header carries the codec name / level, frame geometry, GOP length, view and GOP counts, the
 I-frame transform parameters and a CRC-32 of every entropy table, which a reader checks against
-its own model before decoding.
+its own model before decoding. height / width are the coded (padded) size; a file coded from 8-bit
+YUV (transcode.py) also carries display_height / display_width, pixfmt, fps and frames (make_header).
 """
 from __future__ import annotations
 
@@ -139,6 +140,12 @@ class ContainerWriter:
     def write_pframe(self, view, gop, frame, payload: bytes):
         self._record(b"P", view, gop, frame, payload)
 
+    def write_payload(self, kind: bytes, view, gop, frame, payload: bytes):
+        """A record whose payload (iframe_payload / pframe_payload) was serialised earlier."""
+        if kind not in (b"I", b"P"):
+            raise ValueError(f"unknown record kind {kind!r}")
+        self._record(kind, view, gop, frame, payload)
+
     def close(self):
         pos = self.f.tell()
         self.f.write(struct.pack("<I", len(self.index)))
@@ -177,6 +184,45 @@ class ContainerReader:
         return sorted({(e[1], e[2]) for e in self.index})
 
 
+def make_header(model, height, width, gop, gops, framing, q, display=None, pixfmt=None, fps=None, frames=None):
+    """The container header. height / width are the coded (padded) size. Optional keys, absent
+    from a file of float RGB frames at the coded size: display = (h, w) -> display_height /
+    display_width (what a decoder crops to), pixfmt = {"chroma": "420", "matrix", "range"} (the
+    source's 8-bit format, which a decoder converts back to), fps = (num, den), frames (total)."""
+    header = {"codec": model.name, "level": model.compression_level, "height": height, "width": width, "gop": gop,
+              "gops": gops, "tables_crc32": tables_crc(model), "framing": framing,
+              "iframe": {"transform": "rct+legall53", "levels": IF.LEVELS, "block": IF.BLOCK,
+                         "band_rows": IF.BAND_ROWS, "q": q}}
+    if display is not None:
+        header["display_height"], header["display_width"] = int(display[0]), int(display[1])
+    if pixfmt is not None:
+        header["pixfmt"] = {"chroma": "420", "matrix": pixfmt["matrix"], "range": pixfmt["range"]}
+    if fps is not None:
+        header["fps"] = [int(fps[0]), int(fps[1])]
+    if frames is not None:
+        header["frames"] = int(frames)
+    return header
+
+
+def display_size(header):
+    """(display_height, display_width); the coded size for a file without display geometry."""
+    H, W = header["height"], header["width"]
+    h, w = header.get("display_height", H), header.get("display_width", W)
+    if not (1 <= h <= H and 1 <= w <= W):
+        raise ValueError(f"display size {h}x{w} does not fit the coded size {H}x{W}")
+    return h, w
+
+
+def info(data: bytes) -> dict:
+    """What a container holds, from its header and index alone (no model, no GPU)."""
+    r = ContainerReader(data)
+    h, w = display_size(r.header)
+    kinds = [e[0] for e in r.index]
+    return {"header": r.header, "display": [h, w], "coded": [r.header["height"], r.header["width"]],
+            "gops": len(r.gops()), "records": len(r.index), "iframes": kinds.count(b"I"),
+            "pframes": kinds.count(b"P"), "bytes": len(r.data)}
+
+
 def encode_video(model, video: torch.Tensor, f, iframe_q=None, framing="segment", views=None):
     """Encode video [N, T, 3, H, W] (N GOPs, H and W multiples of 64) into container file f.
     GOP n is muxed as (view = views[n] if given else 0, gop = n). Frame 0 of each GOP is coded by
@@ -185,11 +231,7 @@ def encode_video(model, video: torch.Tensor, f, iframe_q=None, framing="segment"
     decoder will hold). Returns the encoder's reconstructions [N, T, 3, H, W]."""
     N, T, C, H, W = video.shape
     q = IF.iframe_step(model.I_level) if iframe_q is None else int(iframe_q)
-    header = {"codec": model.name, "level": model.compression_level, "height": H, "width": W, "gop": T,
-              "gops": N, "tables_crc32": tables_crc(model), "framing": framing,
-              "iframe": {"transform": "rct+legall53", "levels": IF.LEVELS, "block": IF.BLOCK,
-                         "band_rows": IF.BAND_ROWS, "q": q}}
-    w = ContainerWriter(f, header)
+    w = ContainerWriter(f, make_header(model, H, W, T, N, framing, q))
     recons = torch.empty_like(video)
     for n in range(N):
         v = 0 if views is None else int(views[n])

@@ -426,6 +426,32 @@ int fvc_torchac_encode(const uint32_t* lo, const uint32_t* hi, int64_t n, uint8_
 int fvc_torchac_decode(const uint16_t* cdf, int Lp, const int32_t* rows, int64_t nrows, int64_t n,
                        const uint8_t* in, size_t len, int16_t* sym);
 
+/* ------------------------------------------------------------------ 8-bit YUV 4:2:0 in and out
+ * Planes: Y [batch][h][w], U and V [batch][(h+1)/2][(w+1)/2], uint8, chroma centre-sited.
+ * RGB: float32 NCHW [batch][3][hp][wp] in [0,1]; hp >= h and wp >= w, both multiples of 64, base
+ * 16-byte aligned. matrix / range pick the coefficients (fvc_pixfmt_coeffs, host, no device).
+ * yuv420_to_rgb_pad: chroma upsampled bilinearly (weights 9/3/3/1, neighbour indices clamped to the
+ *   plane, exact in 1/16 units), float32 matrix from Y - offset and C16 - 2048, clamp to [0,1];
+ *   pixel (r, c) with r >= h or c >= w repeats pixel (min(r, h-1), min(c, w-1)) (replicate pad).
+ * rgb_to_yuv420_crop: the top-left h x w only. c8 = rint(clamp(x,0,1) * 255); each of Y, U, V is
+ *   clamp((row . rgb8 + (offset << 16) + 32768) >> 16, 0, 255) with the 16-fractional-bit rows
+ *   fwd9; a chroma sample is (a+b+c+d+2) >> 2 over its 2x2 pixels' chroma, rows / columns clamped
+ *   to h-1 / w-1. Integer throughout: exact.
+ * pixfmt_coeffs: fwd9 = rint(M * 65536) with each row's largest-magnitude entry adjusted so the
+ *   luma row sums to rint(s_y * 65536) and the chroma rows to 0 (grey survives exactly);
+ *   offs2 = {luma, chroma} offsets; inv5 = {ky, rv, gu, gv, bu}: R = ky Y' + rv V', G = ky Y' +
+ *   gu U' + gv V', B = ky Y' + bu U' with Y' = Y - offset, U' / V' = C16 - 2048.
+ * sse_u8: *out (device uint64) = sum (a[i] - b[i])^2 over n bytes; integer atomics, so exact and
+ *   independent of the order of addition. */
+enum { FVC_MATRIX_BT601 = 0, FVC_MATRIX_BT709 = 1 };
+enum { FVC_RANGE_LIMITED = 0, FVC_RANGE_FULL = 1 };
+int fvc_pixfmt_coeffs(int matrix, int range, int32_t* fwd9, int32_t* offs2, float* inv5);
+int fvc_yuv420_to_rgb_pad(const uint8_t* y, const uint8_t* u, const uint8_t* v, float* out, int batch, int h,
+                          int w, int hp, int wp, int matrix, int range, fvc_stream_t stream);
+int fvc_rgb_to_yuv420_crop(const float* x, uint8_t* y, uint8_t* u, uint8_t* v, int batch, int h, int w, int hp,
+                           int wp, int matrix, int range, fvc_stream_t stream);
+int fvc_sse_u8(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* out, fvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
