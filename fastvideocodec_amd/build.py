@@ -19,7 +19,7 @@ SRC_FLAGS = {"fvc_conv_wino.hip": ["-fno-slp-vectorize"], "fvc_conv_wr7.hip": ["
 OUT = os.path.join(HERE, "libfvc.so")
 OBJDIR = os.path.join(HERE, "build")
 HEADERS = [os.path.join(HERE, "csrc", "fvc_common.h"), os.path.join(HERE, "csrc", "fvc_dist.h"),
-           os.path.join(HERE, "csrc", "fvc_dx.h"),
+           os.path.join(HERE, "csrc", "fvc_dx.h"), os.path.join(HERE, "csrc", "fvc_split.h"),
            os.path.join(os.path.dirname(HERE), "include", "fvc.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 

@@ -27,19 +27,11 @@
 // (v_mfma_f32_32x32x16_f16), y = main 2^-kw + corr 2^-kw-11 + bias. An input >= 65520 rounds to an
 // infinite hi part: 0 * (every pre-activation output) is summed and a NaN raises the caller's
 // overflow flag (the host then recomputes on the fp32 kernels), as the Winograd kernels do.
-#include "fvc_common.h"
-#include <math.h>
-#include <stdlib.h>
+#include "fvc_split.h"
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLoScale = 2048.f;
-constexpr unsigned kOob = 0xFFFFFF00u;
-constexpr int kRsrcFlags = 0x00020000;
+using namespace fvc_split;
 
 struct StemArgs {
   const float* x;     // [B][H][W][CINP]
@@ -52,28 +44,7 @@ struct StemArgs {
   int* ovf;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  const unsigned long long v = (unsigned long long)(uintptr_t)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  void* const q = (void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(q, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), kRsrcFlags);
-}
-
-// v = hi + lo * 2^-11 for two values (the x3 / Winograd split)
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
-      "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(hi), "=&v"(r0), "=&v"(r1)
-      : "v"(v0), "v"(v1));
-  asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
-      "v_fma_mixhi_f16 %0, %2, %3, 0"
-      : "=&v"(lo)
-      : "v"(r0), "v"(r1), "s"(kLoScale));
-}
-
+// two pixel quads (8 channels) through split2 into one MFMA operand pair
 __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, h8& hi, h8& lo) {
   unsigned hw[4], lw[4];
   split2(a[0], a[1], hw[0], lw[0]);
@@ -278,17 +249,6 @@ __global__ __launch_bounds__(64 * NW) void conv_stem_kernel(const StemArgs a) {
   if ((chk[0] != 0.f || chk[1] != 0.f || chk[2] != 0.f || chk[3] != 0.f) && a.ovf) atomicOr(a.ovf, 1);
 }
 
-int stem_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
 template <int CINP, int NT, int K, int S, int ACT>
 int stem_launch(StemArgs a, hipStream_t st) {
   // waves per block = output rows per tile: 8 where the input window is large (8-float pixels, 5x5),
@@ -319,7 +279,7 @@ int stem_launch(StemArgs a, hipStream_t st) {
     per_cu = nb;
   }
   const long long want = a.ntiles;
-  const long long cap = (long long)per_cu * stem_cus();
+  const long long cap = (long long)per_cu * fvc_num_cus();
   const int grid = (int)(want < cap ? want : cap);
   hipLaunchKernelGGL((conv_stem_kernel<CINP, NT, K, S, ACT, NW>), dim3(grid), dim3(kThreads), lds, st, a);
   FVC_CHECK_LAUNCH();
@@ -371,13 +331,7 @@ int fvc_conv_stem_pack_weight(const float* w, int cin, int cout, int ksize, void
   const int cinp = stem_cinp(cin), ns = stem_steps(cinp, ksize), nt = cout / 32, kt = ksize * ksize;
   double mx = 0.0;
   for (int i = 0; i < cout * cin * kt; ++i) mx = fabs((double)w[i]) > mx ? fabs((double)w[i]) : mx;
-  int kw = 0;
-  if (mx > 0.0 && isfinite(mx)) {
-    int e;
-    frexp(mx, &e);
-    kw = 14 - e;
-    kw = kw < -100 ? -100 : (kw > 100 ? 100 : kw);
-  }
+  const int kw = fvc_split_kw(mx);
   const float sc = ldexpf(1.f, kw);
   *osc_out = ldexpf(1.f, -kw);
   _Float16* out = (_Float16*)wp;
@@ -389,10 +343,8 @@ int fvc_conv_stem_pack_weight(const float* w, int cin, int cout, int ksize, void
           const int kidx = 16 * st + 8 * (lane >> 5) + e;
           const int tap = kidx / cinp, ci = kidx - tap * cinp;
           const float v = (tap < kt && ci < cin) ? w[((size_t)co * cin + ci) * kt + tap] * sc : 0.f;
-          const _Float16 hi = (_Float16)v;
           const size_t base = ((((size_t)st * nt + n) * 2) * 64 + lane) * 8;
-          out[base + e] = hi;
-          out[base + 64 * 8 + e] = (_Float16)((v - (float)hi) * 2048.f);
+          fvc_split_store(out + base + e, out + base + 64 * 8 + e, v);
         }
       }
   return 0;

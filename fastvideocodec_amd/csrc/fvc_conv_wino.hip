@@ -39,23 +39,11 @@
 // Epilogue forms: plain (bias, ReLU / LeakyReLU, residual add), and POOL, which also writes the
 // 2x2 average pool of the output (each pool window is one Winograd tile: ATen's ((x00 + x01) + x10)
 // + x11) / 4, bit-identical to k_avgpool2).
-#include "fvc_common.h"
-#include <math.h>
-#include <stdlib.h>
+#include "fvc_split.h"
 
 namespace {
 
-// cache policy of the activation stores (aux operand of buffer_store; experiment builds only,
-// e.g. 2 = non-temporal on gfx950)
-#ifndef FVC_STORE_AUX
-#define FVC_STORE_AUX 0
-#endif
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
+using namespace fvc_split;
 
 constexpr int kC = 64;             // input and output channels
 constexpr int kQ = kC / 4;         // channel quads per pixel
@@ -88,7 +76,6 @@ constexpr int kLowBytes = kLowRows * kLowRowEnt * 16;      // 20,480
 constexpr int kLdsUp = kHdr + kRingBytes + kZBytes + kLowBytes;  // 127,488 B
 // items per schedule chunk (consecutive tile rows of one column): 16 (32 as an experiment switch)
 constexpr int kChunkMin = 16, kChunkMax = 32;
-constexpr float kLoScale = 2048.f;
 // knock-outs (experiment builds only; results wrong): FVC_WINO_KO bit 1 = no k-step-1 MFMAs,
 // 2 = no k-step-0 MFMAs (their split VALU kept), 4 = no item barrier, 8 = no finishing pass,
 // 16 = finishing pass without its output stores, 32 = finishing pass without its Z reads,
@@ -115,8 +102,6 @@ constexpr float kLoScale = 2048.f;
 #define FVC_WINO_ALLNOP 0
 #endif
 constexpr bool kAllNop = FVC_WINO_ALLNOP;  // every MFMA block opens with s_nop 1 (diagnostic)
-constexpr unsigned kOob = 0xFFFFFF00u;
-constexpr int kRsrcFlags = 0x00020000;
 constexpr int kPostPool = 1;
 constexpr int kPostTap = 2;
 constexpr int kResPost = 1;
@@ -153,8 +138,6 @@ struct WinoArgs {
   float usy, usx;  // (hl - 1) / (H - 1), (wl - 1) / (W - 1), one correctly rounded float division each
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
 // 16-B entry of (local column c = 0..33, channel quad Q) within a staged row
 __device__ __forceinline__ int ring_entry(int c, int Q) {
   if constexpr (kPix) return c * kQ + (Q ^ ((c >> 1) & 15));
@@ -164,49 +147,7 @@ __device__ __forceinline__ int ring_entry(int c, int Q) {
 // UP: quad swizzle of the low rows' LDS image (pixel p's quad q at slot q ^ low_swz(p))
 __device__ __forceinline__ int low_swz(int p) { return (p & 3) << 2; }
 
-// a raw buffer descriptor over [p, p + bytes): offsets at or past `bytes` read 0 / drop the store.
-// The inputs go through readfirstlane (free on values already in SGPRs): the compiler must see the
-// descriptor as uniform or it wraps every access in a waterfall loop (cdna_hip_programming.md T20).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  const unsigned long long v = (unsigned long long)(uintptr_t)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  void* const q = (void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(q, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), kRsrcFlags);
-}
-
-// The three split-precision products of one (position, 16-channel N-tile) pair:
-//   acc += U_hi V_hi, cor += U_lo V_hi, cor += U_hi V_lo
-// U is an AGPR operand ("a": the 256 resident U registers fill the accumulator half of the file,
-// the k-loop's VGPRs stay free for the transforms); hipcc does not place MFMAs with A/B operands
-// in AGPRs, hence inline asm. Wait states (cdna_hip_programming.md §5.7): a VALU write of vh / vl
-// or a v_accvgpr_write of U right before -> 2 states (s_nop 1, opening the string); the
-// accumulate chains need none; the VALU reads of acc / cor after the item's last MFMA are fenced
-// by wino_mfma_drain.
-// NOP: open with the 2 states (s_nop 1) a VALU-written vh / vl needs; blocks whose operands were
-// written three or more instructions earlier skip it (scripts/check_wino_hazards.py audits the
-// built .s for VALU writes of MFMA sources within 2 states).
-#define WINO_MFMA3_BODY(C0, C1)                    \
-  "v_mfma_f32_16x16x32_f16 %0, %2, %4, " C0 "\n\t" \
-  "v_mfma_f32_16x16x32_f16 %1, %3, %4, " C1 "\n\t" \
-  "v_mfma_f32_16x16x32_f16 %1, %2, %5, %1"
-template <bool FIRST, bool NOP>
-__device__ __forceinline__ void wino_mfma3(f32x4& acc, f32x4& cor, const h8& uh, const h8& ul, const h8& vh,
-                                           const h8& vl) {
-  if constexpr (FIRST) {  // first k-step of an item: the chains start from C = 0
-    if constexpr (NOP)
-      asm volatile("s_nop 1\n\t" WINO_MFMA3_BODY("0", "0") : "=&v"(acc), "=&v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-    else
-      asm volatile(WINO_MFMA3_BODY("0", "0") : "=&v"(acc), "=&v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-  } else {
-    if constexpr (NOP)
-      asm volatile("s_nop 1\n\t" WINO_MFMA3_BODY("%0", "%1") : "+v"(acc), "+v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-    else
-      asm volatile(WINO_MFMA3_BODY("%0", "%1") : "+v"(acc), "+v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-  }
-}
-
-// wino_mfma3 (first k-step) followed by the split of two values of the next k-step (split2's
+// mfma3 (first k-step) followed by the split of two values of the next k-step (split2's
 // instructions): the split's VALU issues while this block's MFMAs run instead of in a cluster of
 // its own. Its outputs feed MFMAs of the next k-step, blocks later.
 #define WINO_MFMA3S_BODY                                                     \
@@ -244,30 +185,6 @@ __device__ __forceinline__ void wino_mfma_drain(f32x4 (&acc)[4][4], f32x4 (&cor)
                "+v"(cor[1][1]), "+v"(cor[1][2]), "+v"(cor[1][3]));
   asm volatile("" : "+v"(cor[2][0]), "+v"(cor[2][1]), "+v"(cor[2][2]), "+v"(cor[2][3]), "+v"(cor[3][0]),
                "+v"(cor[3][1]), "+v"(cor[3][2]), "+v"(cor[3][3]));
-}
-
-// max(x, 0) as one v_max_f32 (fmaxf compiles to a NaN-quieting v_max x, x first)
-__device__ __forceinline__ float relu1(float x) {
-  float r;
-  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
-  return r;
-}
-
-// y = hi + lo * 2^-11 for two values: hi by one packed round-to-nearest conversion, the residual
-// y - hi by v_fma_mix (hi read as f16 inside the FMA: exact), lo rounded straight to f16 by
-// v_fma_mix{lo,hi} (5 VALU per pair instead of 8 for convert / convert back / subtract / scale /
-// convert). Pure VALU asm: the hardware interlocks VALU dependencies.
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
-      "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(hi), "=&v"(r0), "=&v"(r1)
-      : "v"(v0), "v"(v1));
-  asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
-      "v_fma_mixhi_f16 %0, %2, %3, 0"
-      : "=&v"(lo)
-      : "v"(r0), "v"(r1), "s"(kLoScale));
 }
 
 // RES: 0 none, kResPost = y = act(conv + bias) + res (ResBlock), kResPre = y = act(conv + bias + res)
@@ -799,8 +716,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
       auto mfma_q1 = [&](int q, const h8 (&vh)[4], const h8 (&vl)[4]) {  // k-step 1 of position q
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-          if (n == 0 || kAllNop) wino_mfma3<false, true>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
-          else wino_mfma3<false, false>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
+          if (n == 0 || kAllNop) mfma3<false, true>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
+          else mfma3<false, false>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
         }
       };
       float v0[4][8], v1[4][8];
@@ -1022,22 +939,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
   }
 }
 
-static int wino_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
-static int env_int(const char* n, int dflt) {
-  const char* v = getenv(n);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
 template <int IOP, int POST, int RES, int ACT, bool UP = false>
 static int wino_launch4(const WinoArgs& a, int grid, hipStream_t s) {
   const int lds = UP ? kLdsUp : kLds;
@@ -1116,7 +1017,7 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   // rows, later ones 2): FVC_WINO_CHUNK=32 (experiments) measured equal on the 1088x1920 and
   // 544x960 layers and 4-5 % slower on the 272x480 quarters (profiles/r6/wino_ko/chunk.txt).
   // The result does not depend on it.
-  a.chunk = env_int("FVC_WINO_CHUNK", kChunkMin) == kChunkMax ? kChunkMax : kChunkMin;
+  a.chunk = fvc_env_int("FVC_WINO_CHUNK", kChunkMin) == kChunkMax ? kChunkMax : kChunkMin;
   a.chunks_per_col = fvc_cdiv(a.tiles_y, a.chunk);
   a.nchunks = batch * a.ngroups * a.chunks_per_col;
   a.osc = osc;
@@ -1134,10 +1035,9 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   // ATen's align_corners=True scale (in - 1) / (out - 1), as k_up2_add_q16p computes it
   a.usy = h > 1 ? (float)(a.hl - 1) / (float)(h - 1) : 0.f;
   a.usx = w > 1 ? (float)(a.wl - 1) / (float)(w - 1) : 0.f;
-  const int reserve = env_int("FVC_X3_RESERVE", -1) >= 0 ? env_int("FVC_X3_RESERVE", 0) : cu_reserve;
-  const int ncu = wino_num_cus() - (reserve < wino_num_cus() / 2 ? reserve : wino_num_cus() / 2);
+  const int ncu = fvc_persistent_cus(cu_reserve);
   int grid = ncu < a.nchunks ? ncu : a.nchunks;
-  a.sched = (sched && sched_len >= 2 && env_int("FVC_X3_DYN", 1)) ? sched : nullptr;
+  a.sched = fvc_dyn_sched(sched, sched_len, 2);
   if (act != FVC_ACT_NONE && act != FVC_ACT_RELU && act != FVC_ACT_LRELU) return FVC_EINVAL;
   if (tw) return wino_launch<FVC_IN_NONE, kPostTap>(a, act, s, grid);
   if (xl) {
@@ -1154,16 +1054,6 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   }
   if (in_op == FVC_IN_NONE) return wino_launch<FVC_IN_NONE, 0>(a, act, s, grid);
   return wino_launch<FVC_IN_RELU, 0>(a, act, s, grid);
-}
-
-static int x3w_kw(const double* u, size_t n) {
-  double mx = 0.0;
-  for (size_t i = 0; i < n; ++i) mx = fabs(u[i]) > mx ? fabs(u[i]) : mx;
-  if (!(mx > 0.0) || !isfinite(mx)) return 0;
-  int e;
-  frexp(mx, &e);
-  const int kw = 14 - e;  // mx * 2^kw in [2^13, 2^14)
-  return kw < -100 ? -100 : (kw > 100 ? 100 : kw);
 }
 
 }  // namespace
@@ -1194,7 +1084,9 @@ int fvc_conv_wino_pack_weight(const float* w, void* wp, float* osc_out) {
         for (int j = 0; j < 4; ++j)
           U[((size_t)(i * 4 + j) * kC + co) * kC + ci] = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
     }
-  const int kw = x3w_kw(U, (size_t)16 * kC * kC);
+  double mx = 0.0;
+  for (size_t i = 0; i < (size_t)16 * kC * kC; ++i) mx = fabs(U[i]) > mx ? fabs(U[i]) : mx;
+  const int kw = fvc_split_kw(mx);
   const double sc = ldexp(1.0, kw);
   *osc_out = ldexpf(1.f, -kw);
   _Float16* out = (_Float16*)wp;
@@ -1207,10 +1099,8 @@ int fvc_conv_wino_pack_weight(const float* w, void* wp, float* osc_out) {
             for (int e = 0; e < 8; ++e) {
               const int ci = 32 * kk + 8 * (lane >> 4) + e;
               const float v = (float)(U[((size_t)(r * 4 + q) * kC + co) * kC + ci] * sc);
-              const _Float16 hi = (_Float16)v;
               const size_t base = ((((((size_t)r * 4 + q) * 4 + n) * 2 + kk) * 2) * 64 + lane) * 8;
-              out[base + e] = hi;                                               // plane 0
-              out[base + 64 * 8 + e] = (_Float16)((v - (float)hi) * 2048.f);   // plane 1
+              fvc_split_store(out + base + e, out + base + 64 * 8 + e, v);  // planes 0 and 1
             }
           }
   free(U);
@@ -1226,13 +1116,7 @@ int fvc_wino_tap_pack_weight(const float* w, void* wp, float* osc_out, int np) {
   if (!w || !wp || !osc_out || !fvc_wino_tap_wpack_bytes(np)) return FVC_EINVAL;
   double mx = 0.0;
   for (int i = 0; i < np * kC; ++i) mx = fabs((double)w[i]) > mx ? fabs((double)w[i]) : mx;
-  int kt = 0;
-  if (mx > 0.0 && isfinite(mx)) {
-    int e;
-    frexp(mx, &e);
-    kt = 14 - e;
-    kt = kt < -100 ? -100 : (kt > 100 ? 100 : kt);
-  }
+  const int kt = fvc_split_kw(mx);
   const float sc = ldexpf(1.f, kt);
   *osc_out = ldexpf(1.f, -kt);
   _Float16* out = (_Float16*)wp;
@@ -1243,10 +1127,8 @@ int fvc_wino_tap_pack_weight(const float* w, void* wp, float* osc_out, int np) {
         for (int e = 0; e < 8; ++e) {
           const int ci = 32 * kk + 8 * (lane >> 4) + e;
           const float v = r < np ? w[(size_t)r * kC + ci] * sc : 0.f;
-          const _Float16 hi = (_Float16)v;
           const size_t base = ((size_t)((rt * 2 + kk) * 2) * 64 + lane) * 8;
-          out[base + e] = hi;
-          out[base + 64 * 8 + e] = (_Float16)((v - (float)hi) * 2048.f);
+          fvc_split_store(out + base + e, out + base + 64 * 8 + e, v);
         }
       }
   return 0;

@@ -38,13 +38,13 @@
 // waves combine their two positions' M into partial outputs, exchange them through LDS (one barrier
 // per output row, double-buffered) and wave w finishes one (output column parity, 16-channel tile)
 // pair: bias, activation (or the partial-sum forms), 16-B stores.
-#include "fvc_common.h"
-#include <math.h>
-#include <stdlib.h>
+#include "fvc_split.h"
 
 #include <type_traits>
 
 namespace {
+
+using namespace fvc_split;
 
 // experiment knobs (compile-time; the product build uses the defaults): the gap after which quad
 // 1's raw columns are read, and whether waves 0..2 use the 3 + 3-term transform (branch) or every
@@ -68,10 +68,6 @@ namespace {
 #define FVC_WR7_SPREAD 0
 #endif
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
 constexpr int kCi = 32;                         // input channels per launch
 constexpr int kQ = kCi / 4;                     // channel quads
 constexpr int kSlots = 40;                      // column slots per (row, quad) line: 19 even + 19 odd used
@@ -84,9 +80,6 @@ constexpr int kResBytes = 4 * 3 * 64 * 16;             // residual rows (mode 2)
 constexpr int kLds = kHdr + kRawBytes + 2 * kZBytes + 1024 + kResBytes;  // 128,256 (+ the dummy-DMA sink)
 constexpr int kRowsMax = 128;                   // output rows per work item, at most (wr7_rows)
 constexpr int kDist = FVC_WR7_DIST;             // raw rows are staged kDist steps before their transform
-constexpr float kLoScale = 2048.f;
-constexpr unsigned kOob = 0xFFFFFF00u;
-constexpr int kRsrcFlags = 0x00020000;
 constexpr int kModeFull = 0;     // y = act(conv + bias)
 constexpr int kModePartial = 1;  // y = conv (first input-channel half)
 constexpr int kModeAdd = 2;      // y = act(conv + bias + y) (second input-channel half)
@@ -102,56 +95,6 @@ struct Wr7Args {
   int* sched;        // [0] blocks finished, [1] next item: zero on entry, reset by the last block
   int* ovf;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
-// raw buffer descriptor over [p, p + bytes): offsets at or past bytes read 0 / drop the store
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
-  const unsigned long long v = (unsigned long long)(uintptr_t)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  void* const q = (void*)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(q, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), kRsrcFlags);
-}
-
-// The three split-precision products of one (position, kernel row, 16-channel tile):
-// acc += U_hi V_hi, cor += U_lo V_hi + U_hi V_lo. U is an AGPR operand (hipcc does not place MFMA
-// A / B operands in AGPRs, hence asm). Wait states (cdna_hip_programming.md §5.7 item 2): the first
-// block of each kernel row opens with s_nop 1 (a VALU-written V or a v_accvgpr_write of U right
-// before); accumulate chains need none; wr7_drain fences the VALU readers of acc / cor.
-#define WR7_MFMA3_BODY(C0, C1)                     \
-  "v_mfma_f32_16x16x32_f16 %0, %2, %4, " C0 "\n\t" \
-  "v_mfma_f32_16x16x32_f16 %1, %3, %4, " C1 "\n\t" \
-  "v_mfma_f32_16x16x32_f16 %1, %2, %5, %1"
-template <bool FIRST, bool NOP>
-__device__ __forceinline__ void wr7_mfma3(f32x4& acc, f32x4& cor, const h8& uh, const h8& ul, const h8& vh,
-                                          const h8& vl) {
-  if constexpr (FIRST) {
-    if constexpr (NOP)
-      asm volatile("s_nop 1\n\t" WR7_MFMA3_BODY("0", "0") : "=&v"(acc), "=&v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-    else
-      asm volatile(WR7_MFMA3_BODY("0", "0") : "=&v"(acc), "=&v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-  } else {
-    if constexpr (NOP)
-      asm volatile("s_nop 1\n\t" WR7_MFMA3_BODY("%0", "%1") : "+v"(acc), "+v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-    else
-      asm volatile(WR7_MFMA3_BODY("%0", "%1") : "+v"(acc), "+v"(cor) : "a"(uh), "a"(ul), "v"(vh), "v"(vl));
-  }
-}
-
-// y = hi + lo * 2^-11 for two values (fvc_conv_wino.hip's split2: 5 VALU per pair)
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-  float r0, r1;
-  asm("v_cvt_pk_f16_f32 %0, %3, %4\n\t"
-      "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mix_f32 %2, %0, -1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "=&v"(hi), "=&v"(r0), "=&v"(r1)
-      : "v"(v0), "v"(v1));
-  asm("v_fma_mixlo_f16 %0, %1, %3, 0\n\t"
-      "v_fma_mixhi_f16 %0, %2, %3, 0"
-      : "=&v"(lo)
-      : "v"(r0), "v"(r1), "s"(kLoScale));
-}
 
 // One LDS-DMA piece (buffer_load_dwordx4 ... lds: 16 B per lane into LDS at M0 + 16 lane) in
 // inline asm. The builtin form makes hipcc wait for every pending LDS-DMA before each later
@@ -173,12 +116,6 @@ __device__ __forceinline__ void dma_piece(__amdgpu_buffer_rsrc_t rx, unsigned vo
       : "=&s"(keep)
       : "v"(voff), "s"(rx), "s"(base)
       : "memory");
-}
-
-__device__ __forceinline__ float relu1(float x) {
-  float r;
-  asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
-  return r;
 }
 
 template <int I>
@@ -478,9 +415,9 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
               if (DY == 0) acc[pp][n] = cor[pp][n] = f32x4{0.f, 0.f, 0.f, 0.f};
               asm volatile("" : "+v"(acc[pp][n]), "+v"(cor[pp][n]) : "v"(vh[VS][pp]), "v"(vl[VS][pp]));
             } else if (DY == 0 && pp == 0 && n == 0)
-              wr7_mfma3<true, true>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp], vl[VS][pp]);
+              mfma3<true, true>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp], vl[VS][pp]);
             else
-              wr7_mfma3<DY == 0, false>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp],
+              mfma3<DY == 0, false>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp],
                                         vl[VS][pp]);
             gap(blk);
             // NT = 1 has 14 blocks: two gaps' work per block
@@ -564,22 +501,6 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
   }
 }
 
-static int wr7_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
-static int env_int(const char* n, int dflt) {
-  const char* v = getenv(n);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
 // Output rows per work item. An item pays a prologue (9 raw rows staged, 7 transformed) worth
 // about kPrologueRows steady-state rows, so long items amortise it; but a launch's makespan is
 // ceil(items / blocks) item lengths, and one block per CU over 128-row items leaves most of the
@@ -588,7 +509,7 @@ static int env_int(const char* n, int dflt) {
 // every output row is the same for any item height (each row sums the same transformed rows in
 // the same order), so the choice never changes the numbers. FVC_WR7_ROWS forces one (A/B).
 static int wr7_rows(int batch, int h, int ngroups, int blocks) {
-  const int forced = env_int("FVC_WR7_ROWS", 0);
+  const int forced = fvc_env_int("FVC_WR7_ROWS", 0);
   if (forced > 0) return forced < kRowsMax ? forced : kRowsMax;
   constexpr int kPrologueRows = 8;
   int best = kRowsMax;
@@ -679,13 +600,7 @@ int fvc_conv_wr7_pack_weight(const float* w, int cin, int cout, int ci0, int co0
           U[((size_t)(j * 7 + dy) * ncol + co) * kCi + ci] = v;
           mx = fabs(v) > mx ? fabs(v) : mx;
         }
-  int kw = 0;
-  if (mx > 0.0 && isfinite(mx)) {
-    int e;
-    frexp(mx, &e);
-    kw = 14 - e;
-    kw = kw < -100 ? -100 : (kw > 100 ? 100 : kw);
-  }
+  const int kw = fvc_split_kw(mx);
   const double sc = ldexp(1.0, kw);
   *osc_out = ldexpf(1.f, 4 - kw);
   static const int pos[4][2] = {{1, 2}, {3, 4}, {5, 6}, {0, 7}};
@@ -700,9 +615,7 @@ int fvc_conv_wr7_pack_weight(const float* w, int cin, int cout, int ci0, int co0
             for (int e = 0; e < 8; ++e) {
               const int ci = 8 * (lane >> 4) + e;
               const float v = (float)(U[((size_t)(pos[wv][pp] * 7 + dy) * ncol + co) * kCi + ci] * sc);
-              const _Float16 hi = (_Float16)v;
-              out[base + e] = hi;
-              out[base + 64 * 8 + e] = (_Float16)((v - (float)hi) * 2048.f);
+              fvc_split_store(out + base + e, out + base + 64 * 8 + e, v);
             }
           }
   free(U);
@@ -733,8 +646,7 @@ int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float
   a.xp = xp;
   a.yp = yp;
   a.ngroups = fvc_cdiv(w, 32);
-  const int reserve = env_int("FVC_X3_RESERVE", -1) >= 0 ? env_int("FVC_X3_RESERVE", 0) : cu_reserve;
-  const int ncu = wr7_num_cus() - (reserve < wr7_num_cus() / 2 ? reserve : wr7_num_cus() / 2);
+  const int ncu = fvc_persistent_cus(cu_reserve);
   a.rows = wr7_rows(batch, h, a.ngroups, ncu);
   a.chunks_per_col = fvc_cdiv(h, a.rows);
   const long long nch = (long long)batch * a.ngroups * a.chunks_per_col;
@@ -744,7 +656,7 @@ int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float
   a.osc_c = osc * (1.f / 2048.f);
   a.ovf = overflow_flag;
   const int grid = ncu < a.nchunks ? ncu : a.nchunks;
-  a.sched = (sched && sched_len >= 2 && env_int("FVC_X3_DYN", 1)) ? sched : nullptr;
+  a.sched = fvc_dyn_sched(sched, sched_len, 2);
   if (nt == 2) return wr7_launch1<2>(a, mode, act, grid, (hipStream_t)stream);
   return wr7_launch1<1>(a, mode, act, grid, (hipStream_t)stream);
 }

@@ -37,29 +37,15 @@
 //    software-pipelined one k-step ahead together with the LDS reads;
 //  * transposed convs: stride^2 output-parity classes, each a stride-1 conv with a tap subset;
 //  * epilogue: scale + bias, ReLU / LeakyReLU(0.1), residual add, exp; pad channels = 0.
-#include "fvc_common.h"
 #include "fvc_dx.h"
-#include <math.h>
-#include <stdlib.h>
+#include "fvc_split.h"
 
 namespace {
 
-// cache policy of the activation stores (aux operand of buffer_store; experiment builds only,
-// e.g. 2 = non-temporal on gfx950)
-#ifndef FVC_STORE_AUX
-#define FVC_STORE_AUX 0
-#endif
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+using namespace fvc_split;
 
 constexpr int kMaxTapsX = 49;
 
-// Accumulation: two weight planes (hi, lo*2^11) and activations split as hi + lo*2^-11; the
-// correction products go to a second accumulator scaled by 2^-11 at the end. (Measured and
-// rejected, r2: one accumulator with UNSCALED residual halves -- 64 fewer VGPRs, same speed on
-// every geometry (scripts/gpu_x3_variants.sh), but an activation residual below 2^-14 is an
-// fp16 subnormal and small-activation layers lose accuracy: 4.8e-4 relative at |x| ~ 1e-4.)
-constexpr float kLoScale = 2048.f;
 // FVC_X3_KO (compile-time, experiment builds only -- wrong results): knock out parts of the k-loop to
 // find the binding unit. bit 0: no weight loads (registers), bit 1: no staging of later chunks,
 // bit 2: no LDS operand reads (registers), bit 3: no MFMAs, bit 4: weights always from k-step 0
@@ -67,7 +53,7 @@ constexpr float kLoScale = 2048.f;
 #ifndef FVC_X3_KO
 #define FVC_X3_KO 0
 #endif
-constexpr int kKO = FVC_X3_KO;  // activation residual scale
+constexpr int kKO = FVC_X3_KO;
 // FVC_X3_SCHED (compile-time, experiments): how each half-step's instruction stream is ordered.
 // 0: sched_barrier pins [next operands' loads] then [MFMAs]; 1: compiler's own order within a
 // half-step; 2: sched_group_barrier interleave, one load between consecutive MFMAs
@@ -139,36 +125,6 @@ struct X3Args {
   int pt;
 };
 
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-
-template <int IOP>
-__device__ __forceinline__ float in_op_t(float v) {
-  if (IOP == FVC_IN_RELU) return fmaxf(v, 0.f);
-  if (IOP == FVC_IN_ABS) return fabsf(v);
-  if (IOP == FVC_IN_ROUND) return rintf(v);  // torch.round: half-to-even
-  return v;
-}
-
-// v = hi + lo * 2^-11 for 8 values (packed fp16 conversions); mx tracks max |v| for the
-// representability check (|v| < 65000)
-__device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo, float& mx) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const f2v x = {v[i], v[i + 1]};
-    const h2v h = __builtin_convertvector(x, h2v);
-    const f2v back = __builtin_convertvector(h, f2v);
-    const h2v l = __builtin_convertvector((x - back) * kLoScale, h2v);
-    hi[i] = h[0];
-    hi[i + 1] = h[1];
-    lo[i] = l[0];
-    lo[i + 1] = l[1];
-  }
-  mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))),
-                       fmaxf(fmaxf(fabsf(v[4]), fabsf(v[5])), fmaxf(fabsf(v[6]), fabsf(v[7])))));
-}
-
 // FVC_X3_TRACE (compile-time, diagnostic builds only): per wave, s_memtime sums of the k-loop's
 // segments (0 prologue, 1 operand/staging load issue, 2 MFMA blocks, 3 staging split + LDS write,
 // 4 chunk end: leftover staging + barrier, 5 epilogue, 6 whole wave) into g_x3_trace. Each stamp
@@ -207,13 +163,6 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return __builtin_amdgcn_readfirstlane(
       (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)p));
 }
-
-// x and y / res are addressed through buffer descriptors with 32-bit offsets (the host keeps
-// each image's input and each launch's output under 4 GB): a halo pixel outside the image gets an
-// offset past the descriptor's range and loads zeros (the conv's zero padding, no select), and a
-// store whose lane is outside the output is dropped by the same range check -- no branches.
-constexpr unsigned kOob = 0xFFFFFF00u;
-constexpr int kRsrcFlags = 0x00020000;
 
 // Wave grid: the 8 waves form WG groups along N; the 8/WG waves of a group stack vertically,
 // each WM strips x WN N-tiles, and group g owns N-tiles nt0 + g*WN .. +WN-1 of the block. With
@@ -845,11 +794,6 @@ static int x3_floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) 
 static int x3_plane_pix(int ir, int ic) { return ((ir * ic + 15) & ~15) + 4; }
 static size_t x3_tile_bytes(int ir, int ic, int cc) { return (size_t)4 * cc * x3_plane_pix(ir, ic); }
 
-static int env_int(const char* n, int dflt) {
-  const char* v = getenv(n);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
 // Geometry and tile choice. Returns false for layers the x3 path does not take (cinp % 8 != 0,
 // cout <= 4 -> the VALU small-N kernel, > 128 output channels).
 static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg& c) {
@@ -860,18 +804,18 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   // cin padded to 4 (cin 2 / 3: mvEncoder conv1, resEncoder conv1) runs as one zero-extended octet:
   // the staging loads 4 channels per pixel and pads the other 4 with zeros, so no widened copy of
   // the input is needed (FVC_X3_CIN4=0 keeps these layers on the fp32 kernels)
-  if (c.cinp % 8 && !(c.cinp == 4 && env_int("FVC_X3_CIN4", 1))) return false;
+  if (c.cinp % 8 && !(c.cinp == 4 && fvc_env_int("FVC_X3_CIN4", 1))) return false;
   // cout <= 4 (N padded to one 32-wide tile): measured faster than the VALU small-N kernel for the
   // 3x3 / 5x5 layers (Warp_net conv6, mvDecoder conv8, resDecoder deconv4), slower for SpyNet's
   // 7x7 16->2 (scripts/conv_micro.py); FVC_X3_SMALLN=0/1 forces either way
   if (c.coutp <= 4) {
-    const int sn = env_int("FVC_X3_SMALLN", -1);
+    const int sn = fvc_env_int("FVC_X3_SMALLN", -1);
     if (sn == 0 || (sn < 0 && ks > 5)) return false;
   }
   c.ntp = fvc_cdiv(c.coutp, 32);
   if (c.ntp > 4) return false;
   const int pad = ks / 2;
-  c.pt = (!transposed && stride == 1 && c.coutp == 16 && ks >= 3 && env_int("FVC_X3_PT", 1)) ? 1 : 0;
+  c.pt = (!transposed && stride == 1 && c.coutp == 16 && ks >= 3 && fvc_env_int("FVC_X3_PT", 1)) ? 1 : 0;
   if (!transposed) {
     c.nclass = 1;
     c.sin = stride;
@@ -919,7 +863,7 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   // is this pack with one channel chunk. FVC_DX=0 keeps them on this kernel (at pack AND launch).
   c.dx = 0;
   c.wl = 0;
-  if (transposed && stride == 2 && c.nclass == 4 && env_int("FVC_DX", 1) &&
+  if (transposed && stride == 2 && c.nclass == 4 && fvc_env_int("FVC_DX", 1) &&
       (c.cinp == 64 || c.cinp == 96 || c.cinp == 128) && (c.ntp == 2 || c.ntp == 4)) {
     int maxt = 0;
     for (int cl = 0; cl < 4; ++cl) maxt = c.ntaps[cl] > maxt ? c.ntaps[cl] : maxt;
@@ -950,16 +894,16 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   // channel chunk: the largest of 32 / 16 / 8 dividing cinp (shrunk below if the two LDS tile
   // buffers do not fit); FVC_X3_CC overrides for experiments
   c.cc = (c.cinp % 32 == 0) ? 32 : ((c.cinp % 16 == 0) ? 16 : 8);
-  const int want_cc = env_int("FVC_X3_CC", 0);
+  const int want_cc = fvc_env_int("FVC_X3_CC", 0);
   if ((want_cc == 8 || want_cc == 16 || want_cc == 32) && c.cinp % want_cc == 0) c.cc = want_cc;
   // block shape: 8 waves x 2 strips (16 output rows x 32 columns), 2 waves per SIMD;
   // FVC_X3_NW / FVC_X3_WM override for experiments (WM=4 only with 4 waves)
   c.nw = 8;
   // stride-2 convs: one strip per wave (measured 0.22 vs 0.35 ms on the 544x960 128-channel layer:
   // two strips double the halo rows each staged chunk carries)
-  c.wm = env_int("FVC_X3_WM", (!transposed && stride == 2) ? 1 : 2) == 1 ? 1 : 2;
+  c.wm = fvc_env_int("FVC_X3_WM", (!transposed && stride == 2) ? 1 : 2) == 1 ? 1 : 2;
   // weight buffers in LDS (WL): two chunks of the block's fragments, sized for its widest N
-  c.wl = env_int("FVC_X3_WL", 0) ? 1 : 0;
+  c.wl = fvc_env_int("FVC_X3_WL", 0) ? 1 : 0;
   c.wnmax = (c.wm == 1 && !transposed && stride == 2 && c.ntp % 4 == 0) ? 4 : (c.ntp >= 2 ? 2 : 1);
   // shrink the channel chunk, then the strips per wave, until two tile buffers fit in LDS
   for (;;) {
@@ -992,25 +936,11 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   return true;
 }
 
-static int x3_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
-
+// largest weight magnitude -> the pack's power-of-two scale exponent
 static int x3_kw(const float* w, size_t n) {
   float mx = 0.f;
   for (size_t i = 0; i < n; ++i) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
-  if (!(mx > 0.f) || !isfinite(mx)) return 0;
-  int e;
-  frexpf(mx, &e);  // mx = m * 2^e, m in [0.5, 1)
-  int kw = 14 - e;  // mx * 2^kw in [2^13, 2^14)
-  return kw < -100 ? -100 : (kw > 100 ? 100 : kw);
+  return fvc_split_kw(mx);
 }
 
 template <int CC, int WM, int WN, int WG, int IOP, int POST, int NWV, int WL>
@@ -1191,7 +1121,7 @@ static int run_dx(const X3Cfg& c, const float* x, const void* wpack, float osc, 
       for (int q = 0; q < 4; ++q) pp_max = sl[q] > pp_max ? sl[q] : pp_max;
     }
   }
-  const int pair_env = env_int("FVC_DX_PAIR", -1);
+  const int pair_env = fvc_env_int("FVC_DX_PAIR", -1);
   const bool paired = pp_max < (1 << 30) && (pair_env == 1 || (pair_env != 0 && pp_max * 100 <= up_max * 115));
   for (int wv = 0; wv < fvc_dx::kWaves; ++wv)
     for (int j = 0; j < fvc_dx::kMaxWT; ++j)
@@ -1203,10 +1133,9 @@ static int run_dx(const X3Cfg& c, const float* x, const void* wpack, float osc, 
   d.tosc = tosc;
   d.tosc_c = tosc * (1.0f / 2048.f);
   d.pcp = pcp;
-  const int reserve = env_int("FVC_X3_RESERVE", -1) >= 0 ? env_int("FVC_X3_RESERVE", 0) : cu_reserve;
-  const int ncu = x3_num_cus() - (reserve < x3_num_cus() / 2 ? reserve : x3_num_cus() / 2);
+  const int ncu = fvc_persistent_cus(cu_reserve);
   const int grid = ncu < d.nitems ? ncu : d.nitems;
-  d.sched = (sched && sched_len >= 2 && env_int("FVC_X3_DYN", 1)) ? sched : nullptr;
+  d.sched = fvc_dyn_sched(sched, sched_len, 2);
   const size_t lds = fvc_dx::lds_bytes(c.cinp, d.ps);
   return fvc_dx::launch(d, c.cinp, wm, wn, in_op, tap, grid, lds, s);
 }
@@ -1257,7 +1186,7 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   // output tensor reaches 4 GB into launches over sub-batches
   const unsigned long long ybytes = (unsigned long long)batch * a.Ho * a.Wo * ych * 4ull;
   const unsigned long long rbytes = (unsigned long long)batch * a.Ho * a.Wo * a.coutp * 4ull;
-  const long long split_env = env_int("FVC_X3_SPLIT_BYTES", 0);  // tests: force the split path
+  const long long split_env = fvc_env_int("FVC_X3_SPLIT_BYTES", 0);  // tests: force the split path
   const unsigned long long split_at = split_env > 0 ? (unsigned long long)split_env : (1ull << 32) - 4096;
   if (ybytes >= split_at || (res && rbytes >= split_at)) {
     if (batch == 1) return FVC_EINVAL;
@@ -1288,8 +1217,8 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   a.dymin = c.dymin; a.dxmin = c.dxmin;
   const int th = c.th;
   a.ir = (th - 1) * c.sin + 1 + (c.dymax - c.dymin);
-  a.xcd = env_int("FVC_X3_XCD", 1) ? 1 : 0;
-  a.prio = env_int("FVC_X3_PRIO", 0) ? 1 : 0;
+  a.xcd = fvc_env_int("FVC_X3_XCD", 1) ? 1 : 0;
+  a.prio = fvc_env_int("FVC_X3_PRIO", 0) ? 1 : 0;
   a.ic = 31 * c.sin + 1 + (c.dxmax - c.dxmin);
   a.pt = c.pt;
   if (c.pt && (tw || pool)) return FVC_EINVAL;
@@ -1327,17 +1256,17 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   // stride-2 convs (one strip per wave) with 4 N-tiles take all 128 channels per block: the
   // input tile is staged once instead of twice (3x3 s2 128->128 at 544x960: 0.214 -> 0.191 ms)
   int wn = (c.wm == 1 && !transposed && stride == 2 && c.ntp % 4 == 0) ? 4 : (c.ntp >= 2 ? 2 : 1);
-  const int want_wn = (tw || pool) ? c.ntp : env_int("FVC_X3_WN", 0);
+  const int want_wn = (tw || pool) ? c.ntp : fvc_env_int("FVC_X3_WN", 0);
   if (want_wn == 1 || want_wn == 2 || (want_wn == 4 && c.wm == 1)) wn = want_wn;
   while (wn > 1 && c.ntp % wn) wn >>= 1;
   const long long base = (long long)tiles_x * tiles_y * batch * c.nclass;
   if (!want_wn)
-    while (wn > 1 && base * (c.ntp / wn) < 2LL * x3_num_cus()) wn >>= 1;
+    while (wn > 1 && base * (c.ntp / wn) < 2LL * fvc_num_cus()) wn >>= 1;
   if ((tw || pool) && wn != c.ntp) return FVC_EINVAL;
   // two N-groups of 4 waves x 4 strips instead of 8 waves x 2 strips x 2 N-tiles (same block
   // tile: 16 rows x 32 pixels x 64 channels): each weight fragment feeds 4 strips
   int wm = c.wm, wg = 1;
-  if (c.nw == 8 && !c.wl && !tw && !pool && env_int("FVC_X3_WG", 0) == 2 && c.wm == 2 && wn == 2) {
+  if (c.nw == 8 && !c.wl && !tw && !pool && fvc_env_int("FVC_X3_WG", 0) == 2 && c.wm == 2 && wn == 2) {
     wm = 4;
     wn = 1;
     wg = 2;
@@ -1354,19 +1283,15 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   if (lds > 160 * 1024) return FVC_EINVAL;
   // persistent grid: ~one 8-wave block per CU (FVC_X3_BPC blocks per CU), each walking a
   // contiguous run of spatial tiles
-  // cu_reserve CUs are left out of the persistent grid for kernels of other streams (the
-  // latency-bound rANS chains): a block that cannot find a free CU would start only when another
-  // block has finished its whole run, doubling the launch's time (FVC_X3_RESERVE overrides)
-  const int reserve = env_int("FVC_X3_RESERVE", -1) >= 0 ? env_int("FVC_X3_RESERVE", 0) : cu_reserve;
-  const int ncu = x3_num_cus() - (reserve < x3_num_cus() / 2 ? reserve : x3_num_cus() / 2);
+  const int ncu = fvc_persistent_cus(cu_reserve);
   const long long yz = (long long)(c.ntp / nb) * batch;
-  const int bpc = env_int("FVC_X3_BPC", 1);
+  const int bpc = fvc_env_int("FVC_X3_BPC", 1);
   long long gx = ((long long)ncu * bpc + yz - 1) / yz;  // blocks over all (tile, class) items
   if (gx > (long long)tiles_x * tiles_y * c.nclass) gx = (long long)tiles_x * tiles_y * c.nclass;
   if (gx < 1) gx = 1;
   dim3 grid((unsigned)gx, c.ntp / nb, batch);
   // dynamic schedule when the caller's scratch holds the group counters (FVC_X3_DYN=0: static runs)
-  a.sched = (sched && sched_len >= 1 + (long long)grid.y * grid.z && env_int("FVC_X3_DYN", 1)) ? sched : nullptr;
+  a.sched = fvc_dyn_sched(sched, sched_len, 1 + (long long)grid.y * grid.z);
   if (c.wl) {
     switch (c.cc) {
       case 8: return x3_launch_cc<8, 1>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
@@ -1476,13 +1401,13 @@ int fvc_conv_x3_pack_weight(const float* w, void* wp, float* osc_out, int cin, i
               if (ci >= cin) continue;
               const float v = (transposed ? w[(((size_t)ci * cout + jo) * ks + ky) * ks + kx]
                                           : w[(((size_t)jo * cin + ci) * ks + ky) * ks + kx]) * sc;
-              const _Float16 hi = (_Float16)v;
-              out[frag + e] = hi;  // plane 0 (hi): lanes 0..63
               if (kAcc1) {
+                const _Float16 hi = (_Float16)v;
+                out[frag + e] = hi;                                                 // plane 0: hi
                 out[frag + 64 * 8 + e] = (_Float16)(v - (float)hi);                 // plane 1: w - hi
                 out[frag + 128 * 8 + e] = (_Float16)((float)hi * (1.f / 2048.f));  // plane 2: hi 2^-11
               } else {
-                out[frag + 64 * 8 + e] = (_Float16)((v - (float)hi) * 2048.f);  // plane 1: lo * 2^11
+                fvc_split_store(out + frag + e, out + frag + 64 * 8 + e, v);  // planes 0 (lanes 0..63), 1
               }
             }
           }
@@ -1513,9 +1438,8 @@ int fvc_x3_tap_pack_weight(const float* w, void* wp, float* osc_out, int np, int
       for (int t = 0; t < 8; ++t) {
         const int ci = 16 * kb + (t < 4 ? t : t + 4) + 4 * lh;
         const float v = (li < np && ci < cin) ? w[(size_t)li * cin + ci] * sc : 0.f;
-        const _Float16 hi = (_Float16)v;
-        out[((size_t)(kb * 2 + 0) * 64 + lane) * 8 + t] = hi;
-        out[((size_t)(kb * 2 + 1) * 64 + lane) * 8 + t] = (_Float16)((v - (float)hi) * 2048.f);
+        fvc_split_store(out + ((size_t)(kb * 2 + 0) * 64 + lane) * 8 + t,
+                        out + ((size_t)(kb * 2 + 1) * 64 + lane) * 8 + t, v);
       }
     }
   return 0;

@@ -21,25 +21,14 @@
 // or (tap form, 1 strip x all N-tiles per wave-tile) the next layer's tap partials, exactly as
 // fvc_conv_x3.hip's kPostTap.
 #include "fvc_dx.h"
-#include <math.h>
+#include "fvc_split.h"
 
 namespace fvc_dx {
 
-// cache policy of the activation stores (aux operand of buffer_store; experiment builds only,
-// e.g. 2 = non-temporal on gfx950)
-#ifndef FVC_STORE_AUX
-#define FVC_STORE_AUX 0
-#endif
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
+using namespace fvc_split;
 
-constexpr float kLoScale = 2048.f;
-constexpr unsigned kOob = 0xFFFFFF00u;
-constexpr int kRsrcFlags = 0x00020000;
 constexpr int kNT = 512;     // threads per block (8 waves, 2 per SIMD)
 constexpr int kFrag = 128;   // uint4 per (k-step, N-tile): hi and lo planes x 64 lanes
 constexpr int kHdr = 1024;   // LDS header: bias (512 B), staging sink, work-item queue
@@ -51,32 +40,9 @@ constexpr int kHdr = 1024;   // LDS header: bias (512 B), staging sink, work-ite
 #endif
 constexpr int kKO = FVC_DX_KO;
 
-template <int IOP>
-__device__ __forceinline__ float in_op_t(float v) {
-  if (IOP == FVC_IN_RELU) return fmaxf(v, 0.f);
-  if (IOP == FVC_IN_ABS) return fabsf(v);
-  if (IOP == FVC_IN_ROUND) return rintf(v);  // torch.round: half-to-even
-  return v;
-}
-
-// v = hi + lo * 2^-11 for 8 values; mx tracks max |v| (fp16 representability, |v| < 65000)
-__device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo, float& mx) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const f2v x = {v[i], v[i + 1]};
-    const h2v h = __builtin_convertvector(x, h2v);
-    const f2v back = __builtin_convertvector(h, f2v);
-    const h2v l = __builtin_convertvector((x - back) * kLoScale, h2v);
-    hi[i] = h[0];
-    hi[i + 1] = h[1];
-    lo[i] = l[0];
-    lo[i + 1] = l[1];
-  }
-  mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))),
-                       fmaxf(fmaxf(fabsf(v[4]), fabsf(v[5])), fmaxf(fabsf(v[6]), fabsf(v[7])))));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, unsigned bytes) {
+// The plain descriptor (no readfirstlane) this kernel was written and measured with: fvc_split.h's
+// uniform rsrc generates different code here, so this file keeps its own form.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_plain(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, kRsrcFlags);
 }
 
@@ -171,7 +137,7 @@ __global__ __launch_bounds__(kNT) void conv_dx_kernel(const DxArgs a) {
     *reinterpret_cast<h8*>(pl) = lo;
   };
   auto image_rsrc = [&](int b) {
-    return rsrc(a.x + (size_t)b * a.H * a.W * CIN, a.x_bytes);
+    return rsrc_plain(a.x + (size_t)b * a.H * a.W * CIN, a.x_bytes);
   };
 
   if (tid == 0) {
@@ -197,8 +163,8 @@ __global__ __launch_bounds__(kNT) void conv_dx_kernel(const DxArgs a) {
   }
   __syncthreads();
 
-  const __amdgpu_buffer_rsrc_t ry = rsrc(a.y, a.y_bytes);
-  const __amdgpu_buffer_rsrc_t rr = rsrc(a.res, a.res ? a.y_bytes : 0u);
+  const __amdgpu_buffer_rsrc_t ry = rsrc_plain(a.y, a.y_bytes);
+  const __amdgpu_buffer_rsrc_t rr = rsrc_plain(a.res, a.res ? a.y_bytes : 0u);
   int buf = 0;
   for (int k = 0;; ++k) {
     const int it = squeue[k & 3];

@@ -229,6 +229,13 @@ def overflow_flag(device=None) -> torch.Tensor:
     return _OVF[key]
 
 
+def _launch_tail(device):
+    """The trailing arguments of every persistent split-precision conv entry point: cu_reserve, the
+    stream's overflow flag, its schedule scratch and length, the stream."""
+    return (_STATE["cu_reserve"], overflow_flag(device).data_ptr(), sched_scratch(device).data_ptr(), SCHED_LEN,
+            stream_handle())
+
+
 class OverflowProbe:
     """Non-blocking read of a stream's overflow flag: copies it to pinned host memory behind the
     work already queued; ``result()`` waits for that copy only (not the device)."""
@@ -441,26 +448,20 @@ class PackedConv:
             for ci0, co0, nt, mode, up, uo in self.wr7:
                 _lib.call("fvc_conv2d_nhwc_wr7", x.data_ptr() + 4 * ci0, xp, up.data_ptr(), nt, uo,
                           self.bias.data_ptr() + 4 * co0, y.data_ptr() + 4 * co0, yp, B, H, W, mode,
-                          ACT_NONE if mode == 1 else act, _STATE["cu_reserve"], overflow_flag(x.device).data_ptr(),
-                          sched_scratch(x.device).data_ptr(), SCHED_LEN, stream_handle())
+                          ACT_NONE if mode == 1 else act, *_launch_tail(x.device))
         elif wino:
             _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
-                      _ptr(res), y.data_ptr(), None, B, H, W, in_op, act, _STATE["cu_reserve"],
-                      overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(), SCHED_LEN,
-                      stream_handle())
+                      _ptr(res), y.data_ptr(), None, B, H, W, in_op, act, *_launch_tail(x.device))
         elif w128:
             _lib.call("fvc_conv2d_nhwc_wino128", x.data_ptr(), self.upack128.data_ptr(), ctypes.addressof(self.osc4),
-                      self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, _STATE["cu_reserve"],
-                      overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(), SCHED_LEN,
-                      stream_handle())
+                      self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, *_launch_tail(x.device))
             wino = True
         elif self.x3:
             self._check_layout()
             fn = "fvc_deconv2d_nhwc_x3" if self.transposed else "fvc_conv2d_nhwc_x3"
             _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(), _ptr(res),
                       y.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, self.stride, in_op, act, post,
-                      _STATE["cu_reserve"], overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(),
-                      SCHED_LEN, stream_handle())
+                      *_launch_tail(x.device))
         else:
             fn = "fvc_deconv2d_nhwc_f32" if self.transposed else "fvc_conv2d_nhwc_f32"
             _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H,
@@ -505,15 +506,12 @@ class PackedConv:
             ev0.record()
         if self.wino:
             _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
-                      _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, IN_NONE, act, _STATE["cu_reserve"],
-                      overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(), SCHED_LEN,
-                      stream_handle())
+                      _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, IN_NONE, act, *_launch_tail(x.device))
         else:
             self._check_layout()
             _lib.call("fvc_conv2d_nhwc_x3_pool", x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(),
                       _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, act,
-                      _STATE["cu_reserve"], overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(),
-                      SCHED_LEN, stream_handle())
+                      *_launch_tail(x.device))
         if timer is not None:
             ev1.record()
             nbytes = 4 * (x.numel() + y.numel() * (2 if res is not None else 1) + pool.numel()) + \
@@ -548,9 +546,7 @@ class PackedConv:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         _lib.call("fvc_conv2d_nhwc_wino_up", skip.data_ptr(), low.data_ptr(), xs.data_ptr(), self.upack.data_ptr(),
-                  self.uosc, self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, _STATE["cu_reserve"],
-                  overflow_flag(skip.device).data_ptr(), sched_scratch(skip.device).data_ptr(), SCHED_LEN,
-                  stream_handle())
+                  self.uosc, self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, *_launch_tail(skip.device))
         if timer is not None:
             ev1.record()
             # skip + low read, X and y written (the standalone upsample-add's traffic plus the conv's)
@@ -598,15 +594,13 @@ class PackedConv:
         if wino:
             _lib.call("fvc_conv2d_nhwc_wino_tap", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
                       _ptr(res), P.data_ptr(), B, H, W, act, tap.wino_wpack.data_ptr(), tap.wino_osc, tap.pcp,
-                      _STATE["cu_reserve"], overflow_flag(x.device).data_ptr(), sched_scratch(x.device).data_ptr(),
-                      SCHED_LEN, stream_handle())
+                      *_launch_tail(x.device))
         else:
             self._check_layout()
             fn = "fvc_deconv2d_nhwc_x3_tap" if self.transposed else "fvc_conv2d_nhwc_x3_tap"
             _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(), _ptr(res), P.data_ptr(),
                       B, H, W, self.cin, self.cout, self.ksize, self.stride, act, tap.wpack.data_ptr(), tap.osc,
-                      tap.pcp, _STATE["cu_reserve"], overflow_flag(x.device).data_ptr(),
-                      sched_scratch(x.device).data_ptr(), SCHED_LEN, stream_handle())
+                      tap.pcp, *_launch_tail(x.device))
         if timer is not None:
             ev1.record()
             # algorithmic work: this conv + the next layer's MACs (the partial GEMM does all of them)
