@@ -161,28 +161,28 @@ def conv_precision() -> str:
 
 
 @contextlib.contextmanager
+def _override(key, value):
+    """_STATE[key] = value inside the block (None: no override)."""
+    old = _STATE[key]
+    if value is not None:
+        _STATE[key] = value
+    try:
+        yield
+    finally:
+        _STATE[key] = old
+
+
 def precision(p: str | None):
     """Override the conv precision for convs packed / run inside the block (None: no override)."""
     if p is not None and p not in PRECISIONS:
         raise ValueError(p)
-    old = _STATE["precision"]
-    _STATE["precision"] = p if p is not None else old
-    try:
-        yield
-    finally:
-        _STATE["precision"] = old
+    return _override("precision", p)
 
 
-@contextlib.contextmanager
 def cu_reserve(n: int):
     """CUs the split-precision conv's persistent grid leaves to other streams' kernels, for the
     convs launched inside the block (gop.py's pipeline)."""
-    old = _STATE["cu_reserve"]
-    _STATE["cu_reserve"] = int(n)
-    try:
-        yield
-    finally:
-        _STATE["cu_reserve"] = old
+    return _override("cu_reserve", int(n))
 
 
 def rans_streams_per_block() -> int:
@@ -194,39 +194,33 @@ def rans_streams_per_block() -> int:
     return _STATE["rans_spb"]
 
 
-@contextlib.contextmanager
 def rans_throughput(on: bool = True):
-    old = _STATE["rans_spb"]
-    _STATE["rans_spb"] = int(os.environ.get("FVC_RANS_SPB_PIPE", "64")) if on else old
-    try:
-        yield
-    finally:
-        _STATE["rans_spb"] = old
+    return _override("rans_spb", int(os.environ.get("FVC_RANS_SPB_PIPE", "64")) if on else None)
 
 
-_OVF = {}
-_SCHED = {}
+_STREAM_I32 = {}
 SCHED_LEN = 4096
+
+
+def _stream_zeros(what, n, device) -> torch.Tensor:
+    """The device int32[n] called what (zero when made) of the current stream of device."""
+    st = torch.cuda.current_stream(device)
+    key = (what, str(st.device), st.cuda_stream)
+    if key not in _STREAM_I32:
+        _STREAM_I32[key] = torch.zeros(n, dtype=torch.int32, device=st.device)
+    return _STREAM_I32[key]
 
 
 def sched_scratch(device=None) -> torch.Tensor:
     """The x3 conv's dynamic-schedule counters (device int32[SCHED_LEN], zero between launches) of
     the current stream of device: launches on one stream are ordered, so they can share it."""
-    st = torch.cuda.current_stream(device)
-    key = (str(st.device), st.cuda_stream)
-    if key not in _SCHED:
-        _SCHED[key] = torch.zeros(SCHED_LEN, dtype=torch.int32, device=st.device)
-    return _SCHED[key]
+    return _stream_zeros("sched", SCHED_LEN, device)
 
 
 def overflow_flag(device=None) -> torch.Tensor:
     """The split-precision overflow flag (device int32[1]) of the current stream of device: every
     x3 conv launched on that stream ORs 1 into it if it staged |v| >= 65000 (or a non-finite v)."""
-    st = torch.cuda.current_stream(device)
-    key = (str(st.device), st.cuda_stream)
-    if key not in _OVF:
-        _OVF[key] = torch.zeros(1, dtype=torch.int32, device=st.device)
-    return _OVF[key]
+    return _stream_zeros("overflow", 1, device)
 
 
 def _launch_tail(device):
@@ -283,6 +277,41 @@ def _layout_env():
     return tuple(get(k) for k in _LAYOUT_ENV)
 
 
+def _pack_weight(fn, nbytes, w, device, before=(), after=(), nosc=1):
+    """fn(w, *before, pack, scale, *after) into a fresh fp16 pack of nbytes: (the pack on device, its output
+    scale as a float; with nosc > 1 the ctypes float[nosc] itself, since launches take its address)."""
+    pack = torch.empty(nbytes // 2, dtype=torch.float16)
+    osc = (ctypes.c_float * nosc)()
+    _lib.call(fn, w.data_ptr(), *before, pack.data_ptr(), ctypes.addressof(osc), *after)
+    return pack.to(device), (float(osc[0]) if nosc == 1 else osc)
+
+
+def _tap_rows(w, transposed):
+    """The tap-partial rows of a conv (OIHW) / transposed conv (IOHW) weight: [ky][kx][co][ci] as
+    [k * k * cout, cin]."""
+    wt = w.permute(2, 3, 1, 0) if transposed else w.permute(2, 3, 0, 1)
+    return wt.reshape(-1, wt.shape[-1]).contiguous()
+
+
+def _tap_gather(P, layer, act, post, res, y=None):
+    """Sum the tap partials P [B, H, W, pcp] into layer's output (+ bias, res, act, post) with
+    fvc_tap_gather_nhwc; layer is the cout <= 4 conv / transposed conv the partials belong to."""
+    B, H, W, pcp = P.shape
+    if y is None:
+        ho, wo = (H * layer.stride, W * layer.stride) if layer.transposed else (H, W)
+        y = torch.empty((B, ho, wo, cp4(layer.cout)), dtype=torch.float32, device=P.device)
+    _chk(res, y.shape, name="res")
+    nb = 4 * (P.numel() + y.numel() * (2 if res is not None else 1))
+    profiling.timed_hbm("tap_gather", nb, lambda: _lib.call(
+        "fvc_tap_gather_nhwc", P.data_ptr(), pcp, layer.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H, W,
+        layer.cout, layer.ksize, layer.stride, int(layer.transposed), act, post, stream_handle()))
+    return y
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
 class PackedConv:
     """A conv / transposed conv with weights packed once for its HIP kernel: the split-precision
     fp16 x3 kernel where supported (cin padded to a multiple of 8, cout > 4), else fp32 MFMA /
@@ -292,10 +321,7 @@ class PackedConv:
                  device, precision: str | None = None):
         lib = _lib.load()
         w = weight.detach().to("cpu", torch.float32).contiguous()
-        if transposed:
-            cin, cout = w.shape[0], w.shape[1]
-        else:
-            cout, cin = w.shape[0], w.shape[1]
+        cin, cout = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
         precision = precision or conv_precision()
         self.cin, self.cout, self.ksize, self.stride, self.transposed = cin, cout, ksize, stride, transposed
         # cout <= 4 with a wide input (mvDecoder deconv8, 128->2 3x3): N padded to a 32-wide MFMA
@@ -305,82 +331,64 @@ class PackedConv:
         # deconv4 (64->3 5x5 s2) stays direct: 1x1 GEMM 0.57 + gather 0.45 ms vs 0.86 ms direct
         # per 4-frame launch (MI355X, r2). FVC_TAPSUM=0 / 2 disables / forces the tap path for
         # every eligible layer.
-        self.tap = None
+        self.tap, self.stem, self.wr7 = None, None, []
         self.wino = self.dx = self.wino128 = False
         tapsum = os.environ.get("FVC_TAPSUM", "1")
         if (precision == "x3" and cout <= 4 and ksize in (3, 5) and stride == (2 if transposed else 1)
                 and cp4(cin) % 8 == 0 and tapsum != "0" and (tapsum == "2" or (cin >= 128 and not transposed))):
             nt = ksize * ksize
-            wt = w.permute(2, 3, 1, 0) if transposed else w.permute(2, 3, 0, 1)  # [ky][kx][co][ci]
-            self.tap = PackedConv(wt.reshape(nt * cout, cin, 1, 1).contiguous(), torch.zeros(nt * cout), 1, 1,
-                                  False, device, precision="x3")
+            self.tap = PackedConv(_tap_rows(w, transposed).reshape(nt * cout, cin, 1, 1), torch.zeros(nt * cout), 1,
+                                  1, False, device, precision="x3")
             self.x3 = self.tap.x3
             self.bias = bias.detach().to(device, torch.float32).contiguous()
             return
-        self.x3 = precision == "x3" and bool(lib.fvc_conv_x3_supported(cin, cout, ksize, stride, int(transposed)))
+        geo = (cin, cout, ksize, stride, int(transposed))
+        self.x3 = precision == "x3" and bool(lib.fvc_conv_x3_supported(*geo))
         # 64 -> 64 3x3 stride-1 layers (Warp_net's ResBlocks): the Winograd F(2x2,3x3) split-precision
         # kernel (fvc_conv_wino.hip; 2.25x fewer MFMAs); the direct x3 pack stays for the fused tap
         # epilogue. FVC_WINO=0 disables it (A/B, tests).
-        self.wino = (self.x3 and os.environ.get("FVC_WINO", "1") != "0" and
-                     bool(lib.fvc_conv_wino_supported(cin, cout, ksize, stride, int(transposed))))
+        self.wino = (self.x3 and os.environ.get("FVC_WINO", "1") != "0" and bool(lib.fvc_conv_wino_supported(*geo)))
         if self.wino:
-            upack = torch.empty(lib.fvc_conv_wino_wpack_bytes() // 2, dtype=torch.float16)
-            uosc = ctypes.c_float(0.0)
-            _lib.call("fvc_conv_wino_pack_weight", w.data_ptr(), upack.data_ptr(), ctypes.addressof(uosc))
-            self.upack, self.uosc = upack.to(device), float(uosc.value)
+            self.upack, self.uosc = _pack_weight("fvc_conv_wino_pack_weight", lib.fvc_conv_wino_wpack_bytes(), w,
+                                                 device)
         # 128 -> 128 3x3 stride-1 layers (MV stacks): four 64 -> 64 Winograd quarters of the same
         # kernel on 128-channel pixels (fvc_conv2d_nhwc_wino128); FVC_WINO128=0 keeps them direct
         self.wino128 = (self.x3 and os.environ.get("FVC_WINO128", "1") != "0" and
-                        bool(lib.fvc_conv_wino128_supported(cin, cout, ksize, stride, int(transposed))))
+                        bool(lib.fvc_conv_wino128_supported(*geo)))
         if self.wino128:
-            q = torch.empty(lib.fvc_conv_wino128_wpack_bytes() // 2, dtype=torch.float16)
-            self.osc4 = (ctypes.c_float * 4)()
-            _lib.call("fvc_conv_wino128_pack_weight", w.data_ptr(), q.data_ptr(), ctypes.addressof(self.osc4))
-            self.upack128 = q.to(device)
+            self.upack128, self.osc4 = _pack_weight("fvc_conv_wino128_pack_weight",
+                                                    lib.fvc_conv_wino128_wpack_bytes(), w, device, nosc=4)
         # SpyNet's 7x7 stride-1 32->64 / 64->32 / 32->16 layers: Winograd-rows F(2,7) split-precision
         # kernel (fvc_conv_wr7.hip; 1.75x fewer MFMAs), as launches of 32 input x 16 * nt output
         # channels: (ci0, co0, nt, mode, upack, osc); a 64-channel input's second half adds the first
         # half's partial sum (mode 1 then 2). FVC_WR7=0 keeps the direct x3 kernel (A/B, tests).
-        self.wr7 = []
-        if (self.x3 and os.environ.get("FVC_WR7", "1") != "0" and
-                bool(lib.fvc_conv_wr7_supported(cin, cout, ksize, stride, int(transposed)))):
+        if self.x3 and os.environ.get("FVC_WR7", "1") != "0" and bool(lib.fvc_conv_wr7_supported(*geo)):
             nt = 1 if cout == 16 else 2
             for co0 in range(0, cout, 16 * nt):
                 for ci0 in range(0, cin, 32):
                     mode = 0 if cin == 32 else (1 if ci0 == 0 else 2)
-                    up = torch.empty(lib.fvc_conv_wr7_wpack_bytes(nt) // 2, dtype=torch.float16)
-                    uo = ctypes.c_float(0.0)
-                    _lib.call("fvc_conv_wr7_pack_weight", w.data_ptr(), cin, cout, ci0, co0, nt, up.data_ptr(),
-                              ctypes.addressof(uo))
-                    self.wr7.append((ci0, co0, nt, mode, up.to(device), float(uo.value)))
+                    self.wr7.append((ci0, co0, nt, mode, *_pack_weight(
+                        "fvc_conv_wr7_pack_weight", lib.fvc_conv_wr7_wpack_bytes(nt), w, device,
+                        before=(cin, cout, ci0, co0, nt))))
         # small-input stems (cin <= 8 on a 4- or 8-float pixel, cout 64 / 128, 3x3 s1 / s2, 5x5 s2:
         # Warp_net feature_ext, mvEncoder conv1, resEncoder conv1): the streaming split-precision
-        # kernel (fvc_conv_stem.hip); FVC_STEM=0 keeps the direct x3 kernel (A/B, tests)
-        self.stem = None
-        if (self.x3 and os.environ.get("FVC_STEM", "1") != "0" and
-                bool(lib.fvc_conv_stem_supported(cin, cout, ksize, stride, int(transposed)))):
-            sp = torch.empty(lib.fvc_conv_stem_wpack_bytes(cin, cout, ksize) // 2, dtype=torch.float16)
-            so = ctypes.c_float(0.0)
-            _lib.call("fvc_conv_stem_pack_weight", w.data_ptr(), cin, cout, ksize, sp.data_ptr(), ctypes.addressof(so))
-            self.stem = (sp.to(device), float(so.value))
+        # kernel (fvc_conv_stem.hip), as (pack, osc); FVC_STEM=0 keeps the direct x3 kernel (A/B, tests)
+        if self.x3 and os.environ.get("FVC_STEM", "1") != "0" and bool(lib.fvc_conv_stem_supported(*geo)):
+            self.stem = _pack_weight("fvc_conv_stem_pack_weight", lib.fvc_conv_stem_wpack_bytes(cin, cout, ksize), w,
+                                     device, before=(cin, cout, ksize))
         # stride-2 transposed layers on the all-classes kernel (fvc_deconv_x3.hip, conv_dx_kernel)
         self.dx = self.x3 and transposed and bool(lib.fvc_deconv_x3_all_classes(cin, cout, ksize, stride))
         if self.x3:
-            nbytes = lib.fvc_conv_x3_wpack_bytes(cin, cout, ksize, stride, int(transposed))
-            packed = torch.empty(nbytes // 2, dtype=torch.float16)
-            osc = ctypes.c_float(0.0)
-            _lib.call("fvc_conv_x3_pack_weight", w.data_ptr(), packed.data_ptr(), ctypes.addressof(osc), cin, cout,
-                      ksize, stride, int(transposed))
-            self.osc = float(osc.value)
-            self.layout = int(lib.fvc_conv_x3_layout_id(cin, cout, ksize, stride, int(transposed)))
+            self.wpack, self.osc = _pack_weight("fvc_conv_x3_pack_weight", lib.fvc_conv_x3_wpack_bytes(*geo), w,
+                                                device, after=geo)
+            self.layout = int(lib.fvc_conv_x3_layout_id(*geo))
         else:
-            n = lib.fvc_conv_wpack_floats(cin, cout, ksize, stride, int(transposed))
+            n = lib.fvc_conv_wpack_floats(*geo)
             if n == 0:
                 raise ValueError(f"unsupported conv geometry cin={cin} cout={cout} k={ksize} s={stride}")
             packed = torch.empty(n, dtype=torch.float32)
-            _lib.call("fvc_conv_pack_weight", w.data_ptr(), packed.data_ptr(), cin, cout, ksize, stride,
-                      int(transposed))
-        self.wpack = packed.to(device)
+            _lib.call("fvc_conv_pack_weight", w.data_ptr(), packed.data_ptr(), *geo)
+            self.wpack = packed.to(device)
         self.bias = bias.detach().to(device, torch.float32).contiguous()
 
     def _check_layout(self):
@@ -404,85 +412,103 @@ class PackedConv:
             return h * self.stride, w * self.stride
         return h // self.stride, w // self.stride
 
-    def __call__(self, x, in_op=IN_NONE, act=ACT_NONE, post=POST_NONE, res=None, out=None):
+    def _check_input(self, x, even=None, name="x", what=None):
+        """(B, H, W) of the NHWC input x after the checks every launch variant shares; even: H and W
+        must be even (default: for a stride-2 conv); what: the variant's own wording of a refusal."""
         B, H, W, cp = x.shape
+        if even is None:
+            even = self.stride == 2 and not self.transposed
+        odd = even and (H % 2 or W % 2)
+        if what is not None and (cp != cp4(self.cin) or odd):
+            raise ValueError(f"{what} {tuple(x.shape)}")
         if cp != cp4(self.cin):
             raise ValueError(f"conv input has {cp} channels, expected {cp4(self.cin)}")
-        if (not self.transposed) and self.stride == 2 and (H % 2 or W % 2):
+        if odd:
             raise ValueError("stride-2 conv needs even input size")
-        _chk(x, name="x")
-        ho, wo = self.out_hw(H, W)
-        oshape = (B, ho, wo, cp4(self.cout))
+        _chk(x, name=name)
+        return B, H, W
+
+    def family(self, in_op=IN_NONE, post=POST_NONE, res=None, hw=0) -> str:
+        """The kernel family __call__ launches for these arguments on images of hw pixels: "stem" | "wr7" |
+        "wino" (the 64 -> 64 kernel, or the four quarters of a wino128 pack) | "dx" | "x3" | "f32"."""
+        if not self.x3:
+            return "f32"
+        if in_op == IN_NONE and post == POST_NONE and res is None and (self.stem is not None or self.wr7):
+            return "stem" if self.stem is not None else "wr7"  # the plain launch only
+        if in_op in (IN_NONE, IN_RELU) and post == POST_NONE:  # what the Winograd kernels stage
+            # the quarters pay 4 launch tails: at 16 GOPs per launch 136x240 0.58 -> 0.62 ms, 272x480
+            # 1.97 -> 1.72, 544x960 7.46 -> 6.08 (MI355X, profiles/r3/wino128). r3 measured a 100 K gate
+            # bench-neutral against 200 K; r5 +0.8 % (profiles/r5/gate_100k); r6, with the faster
+            # pixel-major Winograd rows, 200 K / 100 K / 30 K = 80.3 / 81.0-81.1 / 81.3-81.4 P-frames/s
+            # (interleaved, profiles/r6/gate_wino128): images of >= 30 K pixels (544x960, 272x480 and
+            # 136x240) take them. Gated per image, not per launch: a frame's result must not depend on
+            # how many frames share its batch.
+            if self.wino or (self.wino128 and res is None and
+                             hw >= int(os.environ.get("FVC_WINO128_MINPIX", "30000"))):
+                return "wino"
+        return "dx" if self.dx else "x3"
+
+    def _record(self, x, suffix, family, floats, dispatches, flops=0.0, nbytes=0):
+        """(flops, key, x3, nbytes, family, dispatches) of a launch on input x, for its ConvRecord. The bytes
+        are floats fp32 values + self.wpack (the direct pack, whichever family ran); flops / nbytes add a
+        fused consumer's share."""
+        B, H, W, _ = x.shape
+        return (profiling.conv_flops(self.cin, self.cout, self.ksize, self.stride, self.transposed, B, H, W) + flops,
+                f"{'deconv' if self.transposed else 'conv'}{self.ksize}s{self.stride} {self.cin}->{self.cout} "
+                f"@{H}x{W}{suffix}", self.x3, 4 * floats + _nbytes(self.wpack) + nbytes, family, dispatches)
+
+    @staticmethod
+    def _dispatches(family, y, res):
+        """Kernel dispatches of a launch that writes y: the direct and all-classes kernels split the batch."""
+        if family not in ("x3", "dx"):
+            return 1
+        return x3_dispatches(y.shape[0], 4 * y[0].numel(), 4 * res[0].numel() if res is not None else 0)
+
+    def __call__(self, x, in_op=IN_NONE, act=ACT_NONE, post=POST_NONE, res=None, out=None):
+        B, H, W = self._check_input(x)
+        oshape = (B, *self.out_hw(H, W), cp4(self.cout))
         _chk(res, oshape, name="res")
         y = out if out is not None else torch.empty(oshape, dtype=torch.float32, device=x.device)
         _chk(y, oshape, name="y")
-        if self.tap is not None:
-            P = self.tap(x, in_op=in_op)  # timed (if a KernelTimer is active) as an x3 launch
-            nb = 4 * (P.numel() + y.numel() * (2 if res is not None else 1))
-            profiling.timed_hbm("tap_gather", nb, lambda: _lib.call(
-                "fvc_tap_gather_nhwc", P.data_ptr(), P.shape[-1], self.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H, W,
-                self.cout, self.ksize, self.stride, int(self.transposed), act, post, stream_handle()))
-            return y
-        timer = profiling.active()
-        if timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        wino = self.wino and in_op in (IN_NONE, IN_RELU) and post == POST_NONE
-        # the quarters pay 4 launch tails: at 16 GOPs per launch 136x240 0.58 -> 0.62 ms, 272x480
-        # 1.97 -> 1.72, 544x960 7.46 -> 6.08 (MI355X, profiles/r3/wino128). r3 measured a 100 K gate
-        # bench-neutral against 200 K; r5 +0.8 % (profiles/r5/gate_100k); r6, with the faster
-        # pixel-major Winograd rows, 200 K / 100 K / 30 K = 80.3 / 81.0-81.1 / 81.3-81.4 P-frames/s
-        # (interleaved, profiles/r6/gate_wino128): images of >= 30 K pixels (544x960, 272x480 and
-        # 136x240) take them. Gated per image, not per launch: a frame's result must not depend on
-        # how many frames share its batch.
-        w128 = (self.wino128 and in_op in (IN_NONE, IN_RELU) and post == POST_NONE and res is None and
-                H * W >= int(os.environ.get("FVC_WINO128_MINPIX", "30000")))
-        wr7 = bool(self.wr7) and in_op == IN_NONE and post == POST_NONE and res is None
-        stem = self.stem is not None and in_op == IN_NONE and post == POST_NONE and res is None
-        if stem:
-            _lib.call("fvc_conv2d_nhwc_stem", x.data_ptr(), self.stem[0].data_ptr(), self.stem[1], self.bias.data_ptr(),
-                      y.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, self.stride, act,
-                      overflow_flag(x.device).data_ptr(), stream_handle())
-        elif wr7:
-            xp, yp = cp4(self.cin), cp4(self.cout)
-            for ci0, co0, nt, mode, up, uo in self.wr7:
-                _lib.call("fvc_conv2d_nhwc_wr7", x.data_ptr() + 4 * ci0, xp, up.data_ptr(), nt, uo,
-                          self.bias.data_ptr() + 4 * co0, y.data_ptr() + 4 * co0, yp, B, H, W, mode,
-                          ACT_NONE if mode == 1 else act, *_launch_tail(x.device))
-        elif wino:
-            _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
-                      _ptr(res), y.data_ptr(), None, B, H, W, in_op, act, *_launch_tail(x.device))
-        elif w128:
-            _lib.call("fvc_conv2d_nhwc_wino128", x.data_ptr(), self.upack128.data_ptr(), ctypes.addressof(self.osc4),
-                      self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, *_launch_tail(x.device))
-            wino = True
-        elif self.x3:
-            self._check_layout()
-            fn = "fvc_deconv2d_nhwc_x3" if self.transposed else "fvc_conv2d_nhwc_x3"
-            _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(), _ptr(res),
-                      y.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, self.stride, in_op, act, post,
-                      *_launch_tail(x.device))
-        else:
-            fn = "fvc_deconv2d_nhwc_f32" if self.transposed else "fvc_conv2d_nhwc_f32"
-            _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H,
-                      W, self.cin, self.cout, self.ksize, self.stride, in_op, act, post, stream_handle())
-        if timer is not None:
-            ev1.record()
-            # algorithmic HBM bytes: input + weights + output (+ residual), each touched once
-            nbytes = 4 * (x.numel() + y.numel() * (2 if res is not None else 1)) + self.wpack.numel() * \
-                self.wpack.element_size()
-            timer.records.append((ev0, ev1, profiling.conv_flops(self.cin, self.cout, self.ksize, self.stride,
-                                                                 self.transposed, B, H, W),
-                                  f"{'deconv' if self.transposed else 'conv'}{self.ksize}s{self.stride} "
-                                  f"{self.cin}->{self.cout} @{H}x{W}{' stem' if stem else (' wr7' if wr7 else (' wino' if wino else (' dx' if self.dx else (' x3' if self.x3 else ''))))}"
-                                  f"{' x4' if w128 else ''}{f' x{len(self.wr7)}' if wr7 and len(self.wr7) > 1 else ''}",
-                                  self.x3, nbytes,
-                                  "stem" if stem else ("wr7" if wr7 else ("wino" if wino else ("dx" if self.dx else ("x3" if self.x3 else "f32")))),
-                                  len(self.wr7) if wr7 else 4 if w128 else (1 if stem or wino or not self.x3 else
-                                                  x3_dispatches(B, 4 * y[0].numel(),
-                                                                4 * res[0].numel() if res is not None else 0))))
-        return y
+        if self.tap is not None:  # the 1x1 GEMM is timed (if a KernelTimer is active) as an x3 launch
+            return _tap_gather(self.tap(x, in_op=in_op), self, act, post, res, y)
+        fam = self.family(in_op, post, res, H * W)
+        # launches of the call: the wr7 sub-blocks, the four quarters of a wino128 pack, else one
+        n = len(self.wr7) if fam == "wr7" else 4 if fam == "wino" and self.wino128 else 1
 
+        def launch():
+            bias = self.bias.data_ptr()
+            if fam == "stem":
+                _lib.call("fvc_conv2d_nhwc_stem", x.data_ptr(), self.stem[0].data_ptr(), self.stem[1], bias,
+                          y.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, self.stride, act,
+                          overflow_flag(x.device).data_ptr(), stream_handle())
+            elif fam == "wr7":
+                xp, yp = cp4(self.cin), cp4(self.cout)
+                for ci0, co0, nt, mode, up, uo in self.wr7:
+                    _lib.call("fvc_conv2d_nhwc_wr7", x.data_ptr() + 4 * ci0, xp, up.data_ptr(), nt, uo, bias + 4 * co0,
+                              y.data_ptr() + 4 * co0, yp, B, H, W, mode, ACT_NONE if mode == 1 else act,
+                              *_launch_tail(x.device))
+            elif fam == "wino" and self.wino:
+                _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc, bias, _ptr(res),
+                          y.data_ptr(), None, B, H, W, in_op, act, *_launch_tail(x.device))
+            elif fam == "wino":
+                _lib.call("fvc_conv2d_nhwc_wino128", x.data_ptr(), self.upack128.data_ptr(),
+                          ctypes.addressof(self.osc4), bias, y.data_ptr(), B, H, W, in_op, act,
+                          *_launch_tail(x.device))
+            elif fam == "f32":
+                fn = "fvc_deconv2d_nhwc_f32" if self.transposed else "fvc_conv2d_nhwc_f32"
+                _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), bias, _ptr(res), y.data_ptr(), B, H, W, self.cin,
+                          self.cout, self.ksize, self.stride, in_op, act, post, stream_handle())
+            else:
+                self._check_layout()
+                fn = "fvc_deconv2d_nhwc_x3" if self.transposed else "fvc_conv2d_nhwc_x3"
+                _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, bias, _ptr(res), y.data_ptr(), B, H, W,
+                          self.cin, self.cout, self.ksize, self.stride, in_op, act, post, *_launch_tail(x.device))
+
+        profiling.timed_conv(launch, lambda: self._record(
+            x, "" if fam == "f32" else f" {fam}" + (f" x{n}" if n > 1 else ""), fam,
+            x.numel() + y.numel() * (2 if res is not None else 1), n if n > 1 else self._dispatches(fam, y, res)))
+        return y
 
     def pool_fusable(self) -> bool:
         return (self.x3 and self.tap is None and not self.transposed and self.stride == 1 and
@@ -492,35 +518,27 @@ class PackedConv:
         """(y, avg_pool2d(y, 2)) from one launch (fvc_conv2d_nhwc_x3_pool; in_op none, post none)."""
         if not self.pool_fusable():
             raise ValueError("conv not poolable in its epilogue")
-        B, H, W, cp = x.shape
-        if cp != cp4(self.cin):
-            raise ValueError(f"conv input has {cp} channels, expected {cp4(self.cin)}")
-        _chk(x, name="x")
+        B, H, W = self._check_input(x)
         oshape = (B, H, W, cp4(self.cout))
         _chk(res, oshape, name="res")
         y = torch.empty(oshape, dtype=torch.float32, device=x.device)
         pool = torch.empty((B, H // 2, W // 2, cp4(self.cout)), dtype=torch.float32, device=x.device)
-        timer = profiling.active()
-        if timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        if self.wino:
-            _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
-                      _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, IN_NONE, act, *_launch_tail(x.device))
-        else:
-            self._check_layout()
-            _lib.call("fvc_conv2d_nhwc_x3_pool", x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(),
-                      _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, act,
-                      *_launch_tail(x.device))
-        if timer is not None:
-            ev1.record()
-            nbytes = 4 * (x.numel() + y.numel() * (2 if res is not None else 1) + pool.numel()) + \
-                self.wpack.numel() * self.wpack.element_size()
-            timer.records.append((ev0, ev1, profiling.conv_flops(self.cin, self.cout, self.ksize, 1, False, B, H, W),
-                                  f"conv{self.ksize}s1 {self.cin}->{self.cout} @{H}x{W} {'wino' if self.wino else 'x3'} +pool",
-                                  True, nbytes, "wino" if self.wino else "x3",
-                                  1 if self.wino else x3_dispatches(B, 4 * y[0].numel(),
-                                                                    4 * res[0].numel() if res is not None else 0)))
+        fam = "wino" if self.wino else "x3"
+
+        def launch():
+            if self.wino:
+                _lib.call("fvc_conv2d_nhwc_wino", x.data_ptr(), self.upack.data_ptr(), self.uosc,
+                          self.bias.data_ptr(), _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, IN_NONE, act,
+                          *_launch_tail(x.device))
+            else:
+                self._check_layout()
+                _lib.call("fvc_conv2d_nhwc_x3_pool", x.data_ptr(), self.wpack.data_ptr(), self.osc,
+                          self.bias.data_ptr(), _ptr(res), y.data_ptr(), pool.data_ptr(), B, H, W, self.cin, self.cout,
+                          self.ksize, act, *_launch_tail(x.device))
+
+        profiling.timed_conv(launch, lambda: self._record(
+            x, f" {fam} +pool", fam, x.numel() + y.numel() * (2 if res is not None else 1) + pool.numel(),
+            self._dispatches(fam, y, res)))
         return y, pool
 
     def up_fusable(self) -> bool:
@@ -534,27 +552,16 @@ class PackedConv:
         bit-identical to upsample2x_add(low, skip)."""
         if not self.up_fusable():
             raise ValueError("conv cannot take the fused upsample-add input")
-        B, H, W, cp = skip.shape
-        if cp != cp4(self.cin) or H % 2 or W % 2:
-            raise ValueError(f"fused upsample-add input: skip {tuple(skip.shape)}")
-        _chk(skip, name="skip")
-        _chk(low, (B, H // 2, W // 2, cp), name="low")
+        B, H, W = self._check_input(skip, even=True, name="skip", what="fused upsample-add input: skip")
+        _chk(low, (B, H // 2, W // 2, skip.shape[-1]), name="low")
         xs = torch.empty_like(skip)
         y = torch.empty((B, H, W, cp4(self.cout)), dtype=torch.float32, device=skip.device)
-        timer = profiling.active()
-        if timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        _lib.call("fvc_conv2d_nhwc_wino_up", skip.data_ptr(), low.data_ptr(), xs.data_ptr(), self.upack.data_ptr(),
-                  self.uosc, self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, *_launch_tail(skip.device))
-        if timer is not None:
-            ev1.record()
-            # skip + low read, X and y written (the standalone upsample-add's traffic plus the conv's)
-            nbytes = 4 * (skip.numel() + low.numel() + xs.numel() + y.numel()) + \
-                self.wpack.numel() * self.wpack.element_size()
-            timer.records.append((ev0, ev1, profiling.conv_flops(self.cin, self.cout, self.ksize, 1, False, B, H, W),
-                                  f"conv{self.ksize}s1 {self.cin}->{self.cout} @{H}x{W} wino +up2add",
-                                  True, nbytes, "wino", 1))
+        # skip + low read, X and y written (the standalone upsample-add's traffic plus the conv's)
+        profiling.timed_conv(lambda: _lib.call(
+            "fvc_conv2d_nhwc_wino_up", skip.data_ptr(), low.data_ptr(), xs.data_ptr(), self.upack.data_ptr(),
+            self.uosc, self.bias.data_ptr(), y.data_ptr(), B, H, W, in_op, act, *_launch_tail(skip.device)),
+            lambda: self._record(skip, " wino +up2add", "wino", skip.numel() + low.numel() + xs.numel() + y.numel(),
+                                 1))
         return y, xs
 
     def _wino_tap(self, tap: "TapConsumer") -> bool:
@@ -577,43 +584,29 @@ class PackedConv:
         ``tap.gather(P, ...)`` finishes the next layer (fvc_conv2d_nhwc_x3_tap)."""
         if not self.tap_fusable(tap):
             raise ValueError("conv / tap pair not fusable")
-        B, H, W, cp = x.shape
-        if cp != cp4(self.cin):
-            raise ValueError(f"conv input has {cp} channels, expected {cp4(self.cin)}")
-        if (not self.transposed) and self.stride == 2 and (H % 2 or W % 2):
-            raise ValueError("stride-2 conv needs even input size")
-        _chk(x, name="x")
+        B, H, W = self._check_input(x)
         ho, wo = self.out_hw(H, W)
         _chk(res, (B, ho, wo, cp4(self.cout)), name="res")
         P = torch.empty((B, ho, wo, tap.pcp), dtype=torch.float32, device=x.device)
-        timer = profiling.active()
-        if timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        wino = self._wino_tap(tap)
-        if wino:
-            _lib.call("fvc_conv2d_nhwc_wino_tap", x.data_ptr(), self.upack.data_ptr(), self.uosc, self.bias.data_ptr(),
-                      _ptr(res), P.data_ptr(), B, H, W, act, tap.wino_wpack.data_ptr(), tap.wino_osc, tap.pcp,
-                      *_launch_tail(x.device))
-        else:
-            self._check_layout()
-            fn = "fvc_deconv2d_nhwc_x3_tap" if self.transposed else "fvc_conv2d_nhwc_x3_tap"
-            _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(), _ptr(res), P.data_ptr(),
-                      B, H, W, self.cin, self.cout, self.ksize, self.stride, act, tap.wpack.data_ptr(), tap.osc,
-                      tap.pcp, *_launch_tail(x.device))
-        if timer is not None:
-            ev1.record()
-            # algorithmic work: this conv + the next layer's MACs (the partial GEMM does all of them)
-            fl = (profiling.conv_flops(self.cin, self.cout, self.ksize, self.stride, self.transposed, B, H, W) +
-                  2.0 * B * ho * wo * tap.cin * tap.np)
-            nbytes = 4 * (x.numel() + P.numel() + (res.numel() if res is not None else 0)) + \
-                self.wpack.numel() * self.wpack.element_size() + tap.wpack.numel() * tap.wpack.element_size()
-            timer.records.append((ev0, ev1, fl, f"{'deconv' if self.transposed else 'conv'}{self.ksize}s{self.stride} "
-                                  f"{self.cin}->{self.cout} @{H}x{W} {'wino' if wino else ('dx' if self.dx else 'x3')} "
-                                  f"+tap{tap.ksize}x{tap.ksize}->{tap.cout}", True, nbytes,
-                                  "wino" if wino else ("dx" if self.dx else "x3"),
-                                  1 if wino else x3_dispatches(B, 4 * P[0].numel(),
-                                                               4 * res[0].numel() if res is not None else 0)))
+        fam = "wino" if self._wino_tap(tap) else "dx" if self.dx else "x3"
+
+        def launch():
+            if fam == "wino":
+                _lib.call("fvc_conv2d_nhwc_wino_tap", x.data_ptr(), self.upack.data_ptr(), self.uosc,
+                          self.bias.data_ptr(), _ptr(res), P.data_ptr(), B, H, W, act, tap.wino_wpack.data_ptr(),
+                          tap.wino_osc, tap.pcp, *_launch_tail(x.device))
+            else:
+                self._check_layout()
+                fn = "fvc_deconv2d_nhwc_x3_tap" if self.transposed else "fvc_conv2d_nhwc_x3_tap"
+                _lib.call(fn, x.data_ptr(), self.wpack.data_ptr(), self.osc, self.bias.data_ptr(), _ptr(res),
+                          P.data_ptr(), B, H, W, self.cin, self.cout, self.ksize, self.stride, act,
+                          tap.wpack.data_ptr(), tap.osc, tap.pcp, *_launch_tail(x.device))
+
+        # algorithmic work: this conv + the next layer's MACs (the partial GEMM does all of them)
+        profiling.timed_conv(launch, lambda: self._record(
+            x, f" {fam} +tap{tap.ksize}x{tap.ksize}->{tap.cout}", fam,
+            x.numel() + P.numel() + (res.numel() if res is not None else 0), self._dispatches(fam, P, res),
+            flops=2.0 * B * ho * wo * tap.cin * tap.np, nbytes=_nbytes(tap.wpack)))
         return P
 
 
@@ -631,40 +624,24 @@ class TapConsumer:
         if cout > 4 or ksize not in (3, 5) or stride != (2 if transposed else 1):
             raise ValueError("tap form needs cout <= 4, k 3/5, conv stride 1 or transposed stride 2")
         self.cin, self.cout, self.ksize, self.stride, self.transposed = cin, cout, ksize, stride, transposed
-        nt = ksize * ksize
-        wt = w.permute(2, 3, 1, 0) if transposed else w.permute(2, 3, 0, 1)  # [ky][kx][co][ci]
-        wt = wt.reshape(nt * cout, cin).contiguous()
-        self.np, self.pcp = nt * cout, cp4(nt * cout)
+        wt = _tap_rows(w, transposed)
+        self.np, self.pcp = wt.shape[0], cp4(wt.shape[0])
         nbytes = lib.fvc_x3_tap_wpack_bytes(self.np, cin)
         if nbytes == 0:
             raise ValueError(f"tap form unsupported: {self.np} partials from {cin} channels")
-        packed = torch.empty(nbytes // 2, dtype=torch.float16)
-        osc = ctypes.c_float(0.0)
-        _lib.call("fvc_x3_tap_pack_weight", wt.data_ptr(), packed.data_ptr(), ctypes.addressof(osc), self.np, cin)
-        self.osc = float(osc.value)
-        self.wpack = packed.to(device)
+        self.wpack, self.osc = _pack_weight("fvc_x3_tap_pack_weight", nbytes, wt, device, after=(self.np, cin))
         # the same rows for the Winograd producer's tap epilogue (64-channel producers only)
         self.wino_wpack, self.wino_osc = None, 0.0
         if cin == 64 and lib.fvc_wino_tap_wpack_bytes(self.np):
-            wp = torch.empty(lib.fvc_wino_tap_wpack_bytes(self.np) // 2, dtype=torch.float16)
-            wosc = ctypes.c_float(0.0)
-            _lib.call("fvc_wino_tap_pack_weight", wt.data_ptr(), wp.data_ptr(), ctypes.addressof(wosc), self.np)
-            self.wino_wpack, self.wino_osc = wp.to(device), float(wosc.value)
+            self.wino_wpack, self.wino_osc = _pack_weight(
+                "fvc_wino_tap_pack_weight", lib.fvc_wino_tap_wpack_bytes(self.np), wt, device, after=(self.np,))
         self.bias = bias.detach().to(device, torch.float32).contiguous()
 
     def gather(self, P, act=ACT_NONE, post=POST_NONE, res=None):
-        B, H, W, pcp = P.shape
-        if pcp != self.pcp:
-            raise ValueError(f"P has {pcp} channels, expected {self.pcp}")
+        if P.shape[-1] != self.pcp:
+            raise ValueError(f"P has {P.shape[-1]} channels, expected {self.pcp}")
         _chk(P, name="P")
-        ho, wo = (H * self.stride, W * self.stride) if self.transposed else (H, W)
-        y = torch.empty((B, ho, wo, cp4(self.cout)), dtype=torch.float32, device=P.device)
-        _chk(res, y.shape, name="res")
-        nb = 4 * (P.numel() + y.numel() * (2 if res is not None else 1))
-        profiling.timed_hbm("tap_gather", nb, lambda: _lib.call(
-            "fvc_tap_gather_nhwc", P.data_ptr(), pcp, self.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H, W,
-            self.cout, self.ksize, self.stride, int(self.transposed), act, post, stream_handle()))
-        return y
+        return _tap_gather(P, self, act, post, res)
 
 
 class GdnTap:
@@ -680,20 +657,16 @@ class GdnTap:
         if cin != 64 or cout > 4 or ksize not in (3, 5) or stride != (2 if transposed else 1) or nt * cout > 128:
             raise ValueError("GDN + tap form needs 64 input channels, cout <= 4, k 3/5, <= 128 partials")
         self.cin, self.cout, self.ksize, self.stride, self.transposed = cin, cout, ksize, stride, transposed
-        wt = (w.permute(2, 3, 1, 0) if transposed else w.permute(2, 3, 0, 1)).reshape(nt * cout, cin).contiguous()
+        wt = _tap_rows(w, transposed)
         self.np, self.pcp = nt * cout, cp4(nt * cout)
         self.ntiles = (self.np + 31) // 32
-        packs, oscs = [], []
+        tiles = []  # (pack, osc) of each 32-row tile
         for t in range(self.ntiles):
             rows = wt[32 * t: 32 * t + 32].contiguous()
-            nbytes = lib.fvc_x3_tap_wpack_bytes(rows.shape[0], cin)
-            pk = torch.empty(nbytes // 2, dtype=torch.float16)
-            osc = ctypes.c_float(0.0)
-            _lib.call("fvc_x3_tap_pack_weight", rows.data_ptr(), pk.data_ptr(), ctypes.addressof(osc), rows.shape[0], cin)
-            packs.append(pk)
-            oscs.append(float(osc.value))
-        self.wpack = torch.cat(packs).to(device)
-        self.osc = (ctypes.c_float * 4)(*(oscs + [0.0] * (4 - len(oscs))))
+            tiles.append(_pack_weight("fvc_x3_tap_pack_weight", lib.fvc_x3_tap_wpack_bytes(rows.shape[0], cin), rows,
+                                      "cpu", after=(rows.shape[0], cin)))
+        self.wpack = torch.cat([pk for pk, _ in tiles]).to(device)
+        self.osc = (ctypes.c_float * 4)(*[osc for _, osc in tiles])  # the launch takes its address
         self.bias = bias.detach().to(device, torch.float32).contiguous()
 
     def __call__(self, x, beta, gamma, inverse, act=ACT_NONE, post=POST_NONE, res=None):
@@ -708,14 +681,7 @@ class GdnTap:
             "fvc_gdn_tap_nhwc", x.data_ptr(), P.data_ptr(), beta.data_ptr(), gamma.data_ptr(), self.wpack.data_ptr(),
             ctypes.addressof(self.osc), self.ntiles, self.pcp, B, H, W, C, int(inverse),
             overflow_flag(x.device).data_ptr(), stream_handle()))
-        ho, wo = (H * self.stride, W * self.stride) if self.transposed else (H, W)
-        y = torch.empty((B, ho, wo, cp4(self.cout)), dtype=torch.float32, device=x.device)
-        _chk(res, y.shape, name="res")
-        nb = 4 * (P.numel() + y.numel() * (2 if res is not None else 1))
-        profiling.timed_hbm("tap_gather", nb, lambda: _lib.call(
-            "fvc_tap_gather_nhwc", P.data_ptr(), self.pcp, self.bias.data_ptr(), _ptr(res), y.data_ptr(), B, H, W,
-            self.cout, self.ksize, self.stride, int(self.transposed), act, post, stream_handle()))
-        return y
+        return _tap_gather(P, self, act, post, res)
 
 
 def x3_overflow(reset: bool = True, device=None) -> bool:

@@ -42,8 +42,7 @@ for name, cin, cout, k, s, tr, h, w, iop, act in CASES:
         continue
     wt = torch.randn((cin, cout, k, k) if tr else (cout, cin, k, k), generator=g) * (1.0 / (cin * k * k) ** 0.5)
     p = K.PackedConv(wt, torch.zeros(cout), k, s, tr, dev, precision="x3")
-    fam = "stem" if p.stem is not None else ("wr7" if p.wr7 else ("wino" if p.wino else ("dx" if p.dx else (
-        "x3" if p.x3 else "f32"))))
+    fam = p.family(in_op=iop, hw=h * w)
     x = torch.rand(1, h, w, K.cp4(cin), device=dev)
     x[..., cin:] = 0
     bad = torch.zeros((), dtype=torch.int64, device=dev)
