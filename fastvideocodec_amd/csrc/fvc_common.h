@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "../../include/fvc.h"
 
 #define FVC_CHECK_LAUNCH()                                   \
@@ -12,6 +13,12 @@
 
 static inline int fvc_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int fvc_rup(int a, int b) { return fvc_cdiv(a, b) * b; }
+
+// integer value of an environment switch; dflt when unset or empty
+static inline int fvc_env_int(const char* n, int dflt) {
+  const char* v = getenv(n);
+  return (v && v[0]) ? atoi(v) : dflt;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

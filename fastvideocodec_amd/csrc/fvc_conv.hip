@@ -22,7 +22,6 @@
 //    the input with a subset of taps (blockIdx.z = batch*classes + class); no zero-insertion.
 //  * epilogue: bias, activation (ReLU / LeakyReLU 0.1), residual add, exp; pad channels = 0.
 #include "fvc_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -62,7 +61,7 @@ struct ChunkGeom {
   static constexpr int CS = (CC4 % 2 == 1) ? CC : CC + 4;  // LDS pixel stride (floats)
 };
 
-template <int CC, int WM, int WN, int BPF>
+template <int CC, int WM, int WN>
 __global__ __launch_bounds__(kThreads) void conv_mfma_f32_kernel(const ConvArgs a) {
   using G = ChunkGeom<CC>;
   constexpr int CC4 = G::CC4;
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void conv_mfma_f32_kernel(const ConvArgs 
     __syncthreads();
 
     const float* wch = wcls + (size_t)ch * kbc * a.ntp * 128;
-    float4 A[WM], Bv[WN], An[WM], Bn[WN], Bnn[WN];
+    float4 A[WM], Bv[WN], An[WM], Bn[WN];
     auto loadA = [&](int q, float4 (&Ar)[WM]) {
       const int kb = 2 * q + lh;
       const int t = kb / CC4;
@@ -150,14 +149,9 @@ __global__ __launch_bounds__(kThreads) void conv_mfma_f32_kernel(const ConvArgs 
     };
     loadA(0, A);
     loadB(0, Bv);
-    if (BPF == 2 && nq > 1) loadB(1, Bn);
     for (int q = 0; q < nq; ++q) {
       if (q + 1 < nq) loadA(q + 1, An);
-      if (BPF == 2) {
-        if (q + 2 < nq) loadB(q + 2, Bnn);
-      } else {
-        if (q + 1 < nq) loadB(q + 1, Bn);
-      }
+      if (q + 1 < nq) loadB(q + 1, Bn);
       // element-major issue order: consecutive MFMAs hit different accumulators (no RAW chain).
       // Weights are the row operand and pixels the column operand, so each lane ends with 4
       // consecutive channels of one pixel per register group (16-B epilogue stores); the two
@@ -181,10 +175,7 @@ __global__ __launch_bounds__(kThreads) void conv_mfma_f32_kernel(const ConvArgs 
 #pragma unroll
       for (int m = 0; m < WM; ++m) A[m] = An[m];
 #pragma unroll
-      for (int n = 0; n < WN; ++n) {
-        Bv[n] = Bn[n];
-        if (BPF == 2) Bn[n] = Bnn[n];
-      }
+      for (int n = 0; n < WN; ++n) Bv[n] = Bn[n];
     }
     __syncthreads();
   }
@@ -230,14 +221,16 @@ __global__ __launch_bounds__(kThreads) void conv_mfma_f32_kernel(const ConvArgs 
 // MFMAs of channel chunk ch out of one buffer, each thread stages one float4 of chunk ch+1 per
 // MFMA quad into the other (global load issued before the quad's MFMAs, LDS write after), so
 // the staging latency hides under the matrix work and only one barrier per chunk remains.
-template <int CC, int WM, int WN, int NW>
-__global__ __launch_bounds__(NW * 64) void conv_mfma_pipe_kernel(const ConvArgs a) {
+// 8 waves per block (kPipeWaves), each WM strips x WN N-tiles.
+constexpr int kPipeWaves = 8;
+template <int CC, int WM, int WN>
+__global__ __launch_bounds__(kPipeWaves * 64) void conv_mfma_pipe_kernel(const ConvArgs a) {
   using G = ChunkGeom<CC>;
   constexpr int CC4 = G::CC4;
   constexpr int CS = G::CS;
-  constexpr int TH = NW * WM;
+  constexpr int TH = kPipeWaves * WM;
   constexpr int TW = 32;
-  constexpr int NT = NW * 64;
+  constexpr int NT = kPipeWaves * 64;
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
   int* tap_off = reinterpret_cast<int*>(smem);
@@ -383,134 +376,6 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_pipe_kernel(const ConvArgs 
         const int ox = qx * a.sout + ox0;
         const size_t o = (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.coutp + j;
         float v = acc[m][n][r] + bj;
-        if (a.act == FVC_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (a.act == FVC_ACT_LRELU) v = v > 0.f ? v : 0.1f * v;
-        if (a.res) v += a.res[o];
-        if (a.post_op == FVC_POST_EXP) v = expf(v);
-        a.y[o] = real ? v : 0.f;
-      }
-    }
-  }
-}
-
-// Stride-2 transposed conv with all four output-parity classes in one block: the four
-// classes read the same input window, so the halo tile of a channel chunk is staged once and
-// consumed by 1+2+2+4 (k=3) or 4+6+6+9 (k=5) taps instead of being re-staged per class.
-// acc[class][WM][WN] stays in registers (WM=1: 4 waves x one 32-pixel strip each).
-template <int CC, int WN>
-__global__ __launch_bounds__(kThreads) void deconv2_mfma_f32_kernel(const ConvArgs a) {
-  using G = ChunkGeom<CC>;
-  constexpr int CC4 = G::CC4;
-  constexpr int CS = G::CS;
-  constexpr int TH = 4;
-  constexpr int TW = 32;
-  constexpr int NCL = 4;
-  constexpr int MAXT = 16;
-
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  int* tap_off = reinterpret_cast<int*>(smem);  // [NCL][MAXT]
-  float* tile = smem + NCL * MAXT;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int li = lane & 31;
-  const int lh = lane >> 5;
-  const int b = blockIdx.z;
-  const int tiles_x = (a.Wq + TW - 1) / TW;
-  const int qy0 = (blockIdx.x / tiles_x) * TH;
-  const int qx0 = (blockIdx.x % tiles_x) * TW;
-  const int nt0 = blockIdx.y * WN;
-
-  if (tid < NCL * MAXT) {
-    const int cl = tid / MAXT, t = tid % MAXT;
-    tap_off[tid] = t < a.ntaps[cl] ? ((a.tdy[cl][t] - a.dymin) * a.ic + (a.tdx[cl][t] - a.dxmin)) * CS : 0;
-  }
-
-  f32x16 acc[NCL][WN];
-#pragma unroll
-  for (int cl = 0; cl < NCL; ++cl)
-#pragma unroll
-    for (int n = 0; n < WN; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[cl][n][r] = 0.f;
-
-  const int iy0 = qy0 + a.dymin;
-  const int ix0 = qx0 + a.dxmin;
-  const int tile_elems = a.ir * a.ic * CC4;
-  const float* xb = a.x + (size_t)b * a.H * a.W * a.cinp;
-  const int pix_base = (wave * a.ic + li) * CS;
-
-  for (int ch = 0; ch < a.nchunks; ++ch) {
-    for (int e = tid; e < tile_elems; e += kThreads) {
-      const int c4 = e % CC4;
-      const int p = e / CC4;
-      const int r = p / a.ic;
-      const int c = p - r * a.ic;
-      const int iy = iy0 + r;
-      const int ix = ix0 + c;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
-        v = *reinterpret_cast<const float4*>(xb + ((size_t)iy * a.W + ix) * a.cinp + ch * CC + c4 * 4);
-        v = fvc_in_op_sel4(v, a.in_op);
-      }
-      *reinterpret_cast<float4*>(tile + p * CS + c4 * 4) = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int cl = 0; cl < NCL; ++cl) {
-      const int kbc = a.kbc[cl];
-      const int ntaps = a.ntaps[cl];
-      const int nq = kbc >> 1;
-      const float* wch = a.w + a.wcls[cl] + (size_t)ch * kbc * a.ntp * 128;
-      const int* toffs = tap_off + cl * MAXT;
-      float4 A, An, Bv[WN], Bn[WN];
-      auto load = [&](int q, float4& Ar, float4 (&Br)[WN]) {
-        const int kb = 2 * q + lh;
-        const int t = kb / CC4;
-        const int c4 = kb - t * CC4;
-        const int toff = (t < ntaps ? toffs[t] : 0) + c4 * 4;
-        Ar = *reinterpret_cast<const float4*>(tile + pix_base + toff);
-        const float* wk = wch + ((size_t)kb * a.ntp + nt0) * 128 + li * 4;
-#pragma unroll
-        for (int n = 0; n < WN; ++n) Br[n] = *reinterpret_cast<const float4*>(wk + n * 128);
-      };
-      load(0, A, Bv);
-      for (int q = 0; q < nq; ++q) {
-        if (q + 1 < nq) load(q + 1, An, Bn);
-#pragma unroll
-        for (int n = 0; n < WN; ++n) {
-          acc[cl][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.x, Bv[n].x, acc[cl][n], 0, 0, 0);
-          acc[cl][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.y, Bv[n].y, acc[cl][n], 0, 0, 0);
-          acc[cl][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.z, Bv[n].z, acc[cl][n], 0, 0, 0);
-          acc[cl][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.w, Bv[n].w, acc[cl][n], 0, 0, 0);
-        }
-        A = An;
-#pragma unroll
-        for (int n = 0; n < WN; ++n) Bv[n] = Bn[n];
-      }
-    }
-    __syncthreads();
-  }
-
-  const int qy = qy0 + wave;
-  if (qy >= a.Hq) return;
-#pragma unroll
-  for (int cl = 0; cl < NCL; ++cl) {
-    const int oy = qy * 2 + a.oy0[cl];
-#pragma unroll
-    for (int n = 0; n < WN; ++n) {
-      const int j = (nt0 + n) * 32 + li;
-      if (j >= a.coutp) continue;
-      const bool real = j < a.cout;
-      const float bj = real ? a.bias[j] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qx = qx0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (qx >= a.Wq) continue;
-        const int ox = qx * 2 + a.ox0[cl];
-        const size_t o = (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.coutp + j;
-        float v = acc[cl][n][r] + bj;
         if (a.act == FVC_ACT_RELU) v = v > 0.f ? v : 0.f;
         else if (a.act == FVC_ACT_LRELU) v = v > 0.f ? v : 0.1f * v;
         if (a.res) v += a.res[o];
@@ -688,7 +553,7 @@ __global__ __launch_bounds__(kThreads) void conv_smalln_f32_kernel(const ConvArg
 
 // ------------------------------------------------------------------ host-side geometry
 struct Cfg {
-  int cinp, coutp, ntp, cc, wm, wn, nclass, nchunks, smalln, sn_py, fused, th, pipe, nw, lds_bufs;
+  int cinp, coutp, ntp, cc, wm, wn, nclass, nchunks, smalln, sn_py, th, pipe, lds_bufs;
   int sin, sout;
   int ntaps[4], kbc[4], oy0[4], ox0[4];
   int tky[4][kMaxTaps], tkx[4][kMaxTaps];  // kernel tap (ky,kx)
@@ -766,44 +631,15 @@ static bool make_cfg(int cin, int cout, int ks, int stride, int transposed, Cfg&
   c.wn = c.ntp;
   // cout 2/3: MFMA N-tile padding would waste 8-16x -> VALU kernel (stride-1 input steps only)
   c.smalln = (c.coutp <= 4 && c.sin == 1) ? 1 : 0;
-  c.fused = (transposed && stride == 2 && !c.smalln && c.cinp % 8 == 0 && ks <= 5) ? 1 : 0;
-  {
-    // measured: the per-class launch with WN<=2 beats the 4-class fused block (register-bound
-    // at 1 wave/SIMD); keep the fused kernel behind FVC_DECONV_FUSED=1 for experiments.
-    const char* f = getenv("FVC_DECONV_FUSED");
-    c.fused = (f && f[0] == '1') ? c.fused : 0;
-  }
-  c.wm = ((!transposed && stride == 2) || c.fused) ? 1 : 2;
-  {
-    const char* w4 = getenv("FVC_CONV_WM4");
-    if (w4 && w4[0] == '1' && !transposed && stride == 1 && ks == 3 && c.ntp <= 2) c.wm = 4;
-  }
-  if (c.fused) c.wn = (c.ntp % 2 == 0) ? 2 : 1;
-  // channel chunk: largest of {32,16,8,4} dividing cinp whose LDS footprint fits 64 KB
-  int maxt = 0;
-  for (int cl = 0; cl < c.nclass; ++cl) maxt = c.ntaps[cl] > maxt ? c.ntaps[cl] : maxt;
+  c.wm = (!transposed && stride == 2) ? 1 : 2;
   // pipelined (double-buffered) path for stride-1 convs with >= 2 channel chunks
   // measured (scripts/conv_micro.py, MI355X): 3x3 128->128 gains +31 % from the 8-wave
   // pipelined kernel; 3x3 64->64 and the 7x7 layers are faster on the 4-wave single-buffer one.
   c.pipe = (!transposed && stride == 1 && !c.smalln && c.cinp >= 128 && ks <= 3) ? 1 : 0;
-  c.nw = 8;
-  {
-    const char* v = getenv("FVC_CONV_PIPE");
-    if (v && v[0] == '0') c.pipe = 0;
-    const char* v7 = getenv("FVC_CONV_PIPE7");
-    if (v7 && v7[0] == '1' && !transposed && stride == 1 && !c.smalln && c.cinp >= 32) c.pipe = 1;
-    const char* w = getenv("FVC_CONV_NW");
-    if (c.pipe && w && w[0] == '4') c.nw = 4;
-    const char* p1 = getenv("FVC_CONV_PIPE");
-    if (p1 && p1[0] == '1' && !transposed && stride == 1 && !c.smalln && c.cinp >= 32 && ks <= 3) c.pipe = 1;
-    const char* wn2 = getenv("FVC_CONV_WN2");
-    if (wn2 && wn2[0] == '1' && !c.pipe && !c.smalln && !c.fused && c.ntp == 4) c.wn = 2;
-    const char* wn1 = getenv("FVC_CONV_WN1");
-    if (wn1 && wn1[0] == '1' && !c.smalln) c.wn = 1;
-  }
   c.lds_bufs = c.pipe ? 2 : 1;
   c.sn_py = (c.smalln && c.cinp % 32 == 0) ? 2 : 4;
-  c.th = c.smalln ? (kThreads / 32) * c.sn_py : (c.pipe ? c.nw * c.wm : 4 * c.wm);
+  c.th = c.smalln ? (kThreads / 32) * c.sn_py : (c.pipe ? kPipeWaves * c.wm : 4 * c.wm);
+  // channel chunk: largest of {32,16,8,4} dividing cinp whose LDS footprint fits the budget
   int cc = 32;
   for (;; cc >>= 1) {
     if (cc == 4) break;
@@ -821,15 +657,8 @@ static bool make_cfg(int cin, int cout, int ks, int stride, int transposed, Cfg&
       const int kt = kmx <= 3 ? 3 : (kmx <= 5 ? 5 : 7);
       wbytes = (size_t)((kt * nxm * cc * 4 + 3) & ~3) * 4 + (size_t)(kt - 1) * ic * cs * 4;
     }
-    const size_t budget = (c.pipe && c.nw == 8) ? 100 * 1024 : (c.smalln && c.sn_py == 2 ? 112 * 1024 : 64 * 1024);
+    const size_t budget = c.pipe ? 100 * 1024 : (c.smalln && c.sn_py == 2 ? 112 * 1024 : 64 * 1024);
     if ((size_t)c.lds_bufs * (((size_t)ir * ic * cs + 3) & ~(size_t)3) * 4 + 256 + wbytes <= budget) break;
-  }
-  {
-    const char* vcc = getenv("FVC_CONV_CC");  // experiment override (must stay fixed per process)
-    if (vcc && !c.smalln && !c.fused) {
-      const int want = atoi(vcc);
-      if ((want == 8 || want == 16 || want == 32) && c.cinp % want == 0) cc = want;
-    }
   }
   c.cc = cc;
   c.nchunks = c.cinp / cc;
@@ -846,18 +675,9 @@ static bool make_cfg(int cin, int cout, int ks, int stride, int transposed, Cfg&
   return true;
 }
 
-static int g_bpf = -1;
-
 template <int CC, int WM, int WN>
 static int launch_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (g_bpf < 0) {
-    const char* v = getenv("FVC_CONV_BPF");
-    g_bpf = (v && v[0] == '2') ? 2 : 1;  // measured: 2-deep weight prefetch is 2-4 % slower
-  }
-  if (g_bpf == 2)
-    hipLaunchKernelGGL((conv_mfma_f32_kernel<CC, WM, WN, 2>), grid, dim3(kThreads), lds, s, a);
-  else
-    hipLaunchKernelGGL((conv_mfma_f32_kernel<CC, WM, WN, 1>), grid, dim3(kThreads), lds, s, a);
+  hipLaunchKernelGGL((conv_mfma_f32_kernel<CC, WM, WN>), grid, dim3(kThreads), lds, s, a);
   FVC_CHECK_LAUNCH();
   return 0;
 }
@@ -876,11 +696,6 @@ static int launch_wn(int wn, const ConvArgs& a, dim3 grid, size_t lds, hipStream
 template <int CC>
 static int launch_wm(int wm, int wn, const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   if (wm == 1) return launch_wn<CC, 1>(wn, a, grid, lds, s);
-  if (wm == 4) {
-    if (wn == 1) return launch_t<CC, 4, 1>(a, grid, lds, s);
-    if (wn == 2) return launch_t<CC, 4, 2>(a, grid, lds, s);
-    return FVC_EINVAL;
-  }
   return launch_wn<CC, 2>(wn, a, grid, lds, s);
 }
 
@@ -920,63 +735,31 @@ static int launch_sn_n(int cout, int kmax, int py, const ConvArgs& a, dim3 grid,
   return FVC_EINVAL;
 }
 
-template <int CC, int WN, int NW>
+template <int CC, int WN>
 static int launch_pp_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)conv_mfma_pipe_kernel<CC, 2, WN, NW>,
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)conv_mfma_pipe_kernel<CC, 2, WN>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((conv_mfma_pipe_kernel<CC, 2, WN, NW>), grid, dim3(NW * 64), lds, s, a);
+  hipLaunchKernelGGL((conv_mfma_pipe_kernel<CC, 2, WN>), grid, dim3(kPipeWaves * 64), lds, s, a);
   FVC_CHECK_LAUNCH();
   return 0;
 }
 
-template <int CC, int NW>
+template <int CC>
 static int launch_pp_wn(int wn, const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
   switch (wn) {
-    case 1: return launch_pp_t<CC, 1, NW>(a, grid, lds, s);
-    case 2: return launch_pp_t<CC, 2, NW>(a, grid, lds, s);
-    case 3: return launch_pp_t<CC, 3, NW>(a, grid, lds, s);
-    case 4: return launch_pp_t<CC, 4, NW>(a, grid, lds, s);
+    case 1: return launch_pp_t<CC, 1>(a, grid, lds, s);
+    case 2: return launch_pp_t<CC, 2>(a, grid, lds, s);
+    case 3: return launch_pp_t<CC, 3>(a, grid, lds, s);
+    case 4: return launch_pp_t<CC, 4>(a, grid, lds, s);
   }
   return FVC_EINVAL;
 }
 
-static int launch_pipe(int cc, int wn, int nw, const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (nw == 8) {
-    switch (cc) {
-      case 8: return launch_pp_wn<8, 8>(wn, a, grid, lds, s);
-      case 16: return launch_pp_wn<16, 8>(wn, a, grid, lds, s);
-      case 32: return launch_pp_wn<32, 8>(wn, a, grid, lds, s);
-    }
-  } else {
-    switch (cc) {
-      case 8: return launch_pp_wn<8, 4>(wn, a, grid, lds, s);
-      case 16: return launch_pp_wn<16, 4>(wn, a, grid, lds, s);
-      case 32: return launch_pp_wn<32, 4>(wn, a, grid, lds, s);
-    }
-  }
-  return FVC_EINVAL;
-}
-
-template <int CC, int WN>
-static int launch_fd_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((deconv2_mfma_f32_kernel<CC, WN>), grid, dim3(kThreads), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
-}
-
-static int launch_fused(int cc, int wn, const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (wn == 1) {
-    switch (cc) {
-      case 8: return launch_fd_t<8, 1>(a, grid, lds, s);
-      case 16: return launch_fd_t<16, 1>(a, grid, lds, s);
-      case 32: return launch_fd_t<32, 1>(a, grid, lds, s);
-    }
-  } else {
-    switch (cc) {
-      case 8: return launch_fd_t<8, 2>(a, grid, lds, s);
-      case 16: return launch_fd_t<16, 2>(a, grid, lds, s);
-      case 32: return launch_fd_t<32, 2>(a, grid, lds, s);
-    }
+static int launch_pipe(int cc, int wn, const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+  switch (cc) {
+    case 8: return launch_pp_wn<8>(wn, a, grid, lds, s);
+    case 16: return launch_pp_wn<16>(wn, a, grid, lds, s);
+    case 32: return launch_pp_wn<32>(wn, a, grid, lds, s);
   }
   return FVC_EINVAL;
 }
@@ -1049,7 +832,7 @@ static int run_conv(const float* x, const float* wpack, const float* bias, const
   const int tiles_y = fvc_cdiv(a.Hq, TH);
   // N-split heuristic (measured, scripts/conv_micro.py): fewer N-tiles per block when the grid
   // would not fill the chip, and at most 2 for the per-class transposed launch.
-  if (!c.smalln && !c.fused && !getenv("FVC_CONV_WN1") && !getenv("FVC_CONV_WN2")) {
+  if (!c.smalln) {
     int wn = c.ntp;
     if (transposed && wn == 4) wn = 2;
     const long long base = (long long)tiles_x * tiles_y * batch * c.nclass;
@@ -1067,13 +850,9 @@ static int run_conv(const float* x, const float* wpack, const float* bias, const
     for (int cl = 0; cl < c.nclass; ++cl) kmax = c.gny[cl] > kmax ? c.gny[cl] : kmax;
     return launch_smalln(c.cc, cout, kmax, c.sn_py, a, grid, dim3(kThreads), lds, s);
   }
-  if (c.fused) {
-    dim3 grid(tiles_x * tiles_y, c.ntp / c.wn, batch);
-    return launch_fused(c.cc, c.wn, a, grid, lds, s);
-  }
   if (c.pipe) {
     dim3 grid(tiles_x * tiles_y, c.ntp / c.wn, batch * c.nclass);
-    return launch_pipe(c.cc, c.wn, c.nw, a, grid, lds, s);
+    return launch_pipe(c.cc, c.wn, a, grid, lds, s);
   }
   dim3 grid(tiles_x * tiles_y, c.ntp / c.wn, batch * c.nclass);
   switch (c.cc) {

@@ -24,7 +24,7 @@
 // Tiling: GEMM M = output pixels (32-pixel strips), N = output channels (32-channel N-tiles),
 // K = taps x input channels walked in k8-blocks = (tap, 8 consecutive channels). One MFMA
 // consumes two k8-blocks: lanes 0-31 hold k8-block 2s, lanes 32-63 hold 2s+1, 8 fp16 each.
-//  * a block = NW waves stacked vertically, each WM strips x WN N-tiles (2 accumulators per
+//  * a block = 8 waves stacked vertically, each WM strips x WN N-tiles (2 accumulators per
 //    tile); grid = (spatial tiles, N-tile groups, batch x parity classes);
 //  * the input halo tile of one channel chunk (CC channels) is staged in LDS as
 //    [pixel][hi CC | lo CC] fp16 with the pixel stride padded to 16 x odd bytes, so the
@@ -105,9 +105,7 @@ struct X3Args {
   int* sched;                      // dynamic schedule (may be null: static runs): sched[0] = blocks
                                    // finished, sched[1 + y * B + z] = next work item of group (y, z);
                                    // zero on entry, reset to zero by the last block
-  int prio;                        // static priority 1 for the second-dispatched half (waves 4-7)
   int* ovf;                        // caller's overflow flag (device int; may be null)
-  int wl_h;                        // WL: halves per LDS weight buffer (the chunk's fragments)
   unsigned res_bytes;              // bytes of res (its own descriptor range)
   // POST == kPostTap: the epilogue applies the next layer's 1x1 tap-partial GEMM to the finished
   // output tile and writes P [B][Ho][Wo][pcp] to y instead of the tile itself
@@ -147,37 +145,12 @@ __device__ __forceinline__ unsigned long long x3_stamp() {
   return t;
 }
 
-// One 1-KB LDS-DMA piece: lane l's 16 B at g land at LDS byte lds + 16 l. Inline asm (M0 saved
-// and restored around it) so the compiler neither sees an LDS write it must drain with vmcnt(0)
-// before every later ds_read nor counts it: the kernel orders it itself (vmcnt(0) before the
-// barrier that precedes the first read of the buffer it fills).
-__device__ __forceinline__ void glds16(const void* g, unsigned lds) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(g), "s"(lds)
-               : "memory");
-}
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return __builtin_amdgcn_readfirstlane(
-      (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)p));
-}
-
-// Wave grid: the 8 waves form WG groups along N; the 8/WG waves of a group stack vertically,
-// each WM strips x WN N-tiles, and group g owns N-tiles nt0 + g*WN .. +WN-1 of the block. With
-// WG = 2, WM = 4, WN = 1 a wave re-uses each weight fragment on 4 strips: half the weight bytes
-// per MFMA of WG = 1, WM = 2, WN = 2 through the vector-memory return path (TD), which the PMC
-// passes show as the kernel's binding unit (scripts/gpu_pmc_x3.sh: TD busy 77 % at 40 % MFMA).
-// WL = 1: the block's weight fragments of each chunk are copied once into LDS by LDS-DMA
-// (global_load_lds, no VGPRs, issued with the chunk's activation staging one chunk ahead) and the
-// waves read them with ds_read_b128 instead of each wave fetching the same 1-KB fragments from L2
-// through the vector-memory return path (8 waves x WN x 2 KB per k-step).
-template <int CC, int WM, int WN, int WG, int IOP, int POST, int NWV, int WL>
+// Wave grid: the NWV waves of a block stack vertically, each WM strips x WN N-tiles; every wave owns
+// the block's N-tiles nt0 .. nt0 + WN - 1 and fetches their weight fragments itself from L2.
+template <int CC, int WM, int WN, int IOP, int POST, int NWV>
 __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
-  constexpr int NW = NWV / WG;       // waves stacked vertically per N-group
   constexpr int C8 = CC / 8;
-  constexpr int TH = NW * WM;
+  constexpr int TH = NWV * WM;
   constexpr int TW = 32;
   constexpr int NT = NWV * 64;       // threads staging the first tile
   constexpr int NTS = NWV * 64;      // threads staging later chunks
@@ -186,11 +159,10 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
   const int tile_h = 2 * C8 * a.ps;  // halves per A buffer: 2*C8 planes (hi octets, lo octets)
   _Float16* const tile0 = smh + 512;  // two buffers at tile0 and tile0 + tile_h (LDS pointers;
                                       // no pointer array, which would degrade them to flat)
-  _Float16* const wbase = tile0 + 2 * tile_h;  // WL: two weight buffers of a.wl_h halves
   // LDS header (1 KB): bias of this block's N-tiles [WN * 32] floats at bytes 0..511, the staging
   // sink at 512..543, the work-item queue at 576..591
   float* const sbias = reinterpret_cast<float*>(smh);
-  static_assert(WG * WN * 32 * 4 <= 512, "bias area");
+  static_assert(WN * 32 * 4 <= 512, "bias area");
   _Float16* const sdump = smh + 256;  // 32 B sink for staging writes of items past the tile
   int* const squeue = reinterpret_cast<int*>(smh) + 144;  // item k of this block at squeue[k & 3]
 
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     finish();
     return;
   }
-  const int nt0 = blockIdx.y * (WG * WN);  // first N-tile of the block
+  const int nt0 = blockIdx.y * WN;  // first N-tile of the block
   int cls = w_first % a.nclass;
   int nq = a.nks[cls];
   const int hf = a.half;
@@ -315,43 +287,22 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     *reinterpret_cast<h8*>(pl) = lo;
   };
 
-  // WL: chunk ch_ of class cls_ -> LDS [k-step][N-tile][hi|lo][lane], one 1-KB piece per
-  // wave-instruction (the LDS destination is the wave-uniform base + 16 B x lane)
-  // piece p = (k-step q, N-tile n, plane pl) of the chunk whose fragments start at src (+ lane)
-  auto w_piece = [&](int p, const uint4* src, _Float16* wdst) {
-    if constexpr (WL != 0) {
-      const int q = p / (WN * kNPL), r = p - q * (WN * kNPL);
-      const int n = r / kNPL, pl = r - n * kNPL;
-      const uint4* g = src + ((size_t)q * a.ntp + nt0 + n) * kFrag + pl * 64;
-      glds16(g, lds_addr(wdst + p * 512));
-    }
-  };
-  auto w_src = [&](int cls_, int ch_) {
-    return a.w + a.wcls[cls_] + (size_t)ch_ * a.nks[cls_] * a.ntp * kFrag + lane;
-  };
-  auto stage_w = [&](int cls_, int ch_, _Float16* wdst) {
-    if constexpr (WL != 0) {
-      const int np = a.nks[cls_] * WN * kNPL;
-      const uint4* src = w_src(cls_, ch_);
-      for (int p = wave; p < np; p += NWV) w_piece(p, src, wdst);
-    }
-  };
-
   for (int e = tid; e < tile_items; e += NT) {
     Stage st;
     fetch(e, w_first / a.nclass, 0, st);
     store(tile0, st);
   }
-  stage_w(cls, 0, wbase);
-  if constexpr (WL != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (tid < WG * WN * 32) {
+  if (tid < WN * 32) {
     const int j = nt0 * 32 + tid;
     sbias[tid] = j < a.cout ? a.bias[j] : 0.f;
   }
 
-  if (a.prio && wave >= NWV / 2) __builtin_amdgcn_s_setprio(1);
-  const int wm_ = wave % NW;                // vertical position of this wave in its group
-  const int wg_ = wave / NW;                // N-group of this wave
+  // Row of this wave in the block's column of NWV waves, and its N-group, which is always 0: wave comes
+  // from readfirstlane, so the compiler cannot see wave < NWV and keeps both as arithmetic. Folding them
+  // by hand (wm_ = wave, ntw = nt0) moves the register allocation of 36 of the 90 instantiations (spill
+  // counts by up to 6 VGPRs either way), so they stay as the compiler has always seen them.
+  const int wm_ = wave % NWV;
+  const int wg_ = wave / NWV;
   const int ntw = nt0 + wg_ * WN;           // first N-tile of this wave
   const int pix0 = (((wm_ * WM) * a.sin) * a.ic + li) * 8;  // strip m adds m * pix_m (halves)
   const int pix_m = a.sin * a.ic * 8;
@@ -404,28 +355,12 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     for (int ch = 0; ch < nch; ++ch) {
       const _Float16* cur = tile0 + buf * tile_h;
       _Float16* nxt = tile0 + (buf ^ 1) * tile_h;
-      const uint4* wcur = reinterpret_cast<const uint4*>(wbase + buf * a.wl_h);
       const bool last = ch + 1 == nch;
       const int s_item = last ? squeue[(k + 1) & 3] : w;
       const int s_tile = s_item / a.nclass;
       const int s_ch = last ? 0 : ch + 1;
       const bool stage_next = s_item < nitems;
       const uint4* wch = wcls + (size_t)ch * nq * a.ntp * kFrag;
-      // WL: this wave's pieces of the next chunk's weights (issued after the chunk's first operand
-      // reads, landed by the vmcnt(0) before the chunk's closing barrier)
-      const int s_cls = s_item % a.nclass;
-      const uint4* wsrc = WL ? w_src(stage_next ? s_cls : 0, s_ch) : nullptr;
-      _Float16* const wdst = wbase + (buf ^ 1) * a.wl_h;
-      const int wnp = (WL && stage_next) ? a.nks[s_cls] * WN * kNPL : 0;
-      int wp = wave;
-      auto w_issue = [&]() {
-        if constexpr (WL != 0) {
-          if (wp < wnp) {
-            w_piece(wp, wsrc, wdst);
-            wp += NWV;
-          }
-        }
-      };
       // k-step q: lane half lh takes k8-block kb = 2q + lh = (tap kb / C8, octet kb % C8)
       auto load = [&](int q, Ops& op) {
         int toff;
@@ -446,8 +381,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
           op.ah[m] = *reinterpret_cast<const h8*>(cur + pix0 + m * pix_m + toff);
           op.al[m] = *reinterpret_cast<const h8*>(cur + pix0 + m * pix_m + toff + C8 * a.ps);
         }
-        const uint4* wk = WL ? wcur + (size_t)q * WN * kFrag + lane
-                             : ((kKO & 16) ? wcls : wch) + ((size_t)((kKO & 16) ? 0 : q) * a.ntp + ntw) * kFrag + lane;
+        const uint4* wk = ((kKO & 16) ? wcls : wch) + ((size_t)((kKO & 16) ? 0 : q) * a.ntp + ntw) * kFrag + lane;
 #pragma unroll
         for (int n = 0; n < WN; ++n) {
           if constexpr ((kKO & 1) != 0) {
@@ -514,7 +448,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
       int staged = 0;
       Ops S0, S1;
       load(0, S0);
-      while (wp < wnp) w_issue();  // WL: the next chunk's weights, a whole chunk ahead
       // staging items of the next chunk are spread evenly over the k-step pairs (one per staged
       // pair) so their VALU work interleaves with MFMA-only steps instead of bunching up at the
       // chunk start, where every wave would be VALU-bound at once
@@ -561,7 +494,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         }
       }
       if (ch == 0 && tid == 0) squeue[(k + 2) & 3] = taken;
-      if constexpr (WL != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's weight DMA
       __syncthreads();
       buf ^= 1;
       TR(4);
@@ -585,7 +517,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     if constexpr (POST == kPostTap) {
       // Fused tap-partial epilogue (the next layer is a cout <= 4 conv computed as a 1x1 GEMM to
       // P = k*k*cout tap partials per pixel + fvc_tap_gather_nhwc). This wave holds every output
-      // channel of its strips (WG = 1, WN = all N-tiles): lane (li, lh) has channel
+      // channel of its strips (WN = all N-tiles): lane (li, lh) has channel
       // 32n + 8g + 4lh + i of pixel li in register 4g + i of tile (m, n), so registers 8gp..8gp+7
       // of tile n are exactly the B operand of the k16 block kb = 2n + gp (channels
       // 32n + 16gp + {0-3, 8-11 | 4-7, 12-15} for lane half 0 | 1; the tap pack uses the same order).
@@ -775,8 +707,6 @@ struct X3Cfg {
   int cinp, coutp, ntp, cc, wm, wn, nw, nclass, nchunks, th, sin, sout;
   int pt;     // pair-tap form (16 output channels, stride 1): (ky, even kx) pairs, see X3Args::pt
   int dx;     // stride-2 transposed conv on fvc_deconv_x3.hip (all classes per staged tile, one chunk)
-  int wl;     // weights staged in LDS by LDS-DMA (FVC_X3_WL; chosen at pack time: it can shrink cc)
-  int wnmax;  // N-tiles per block the LDS weight buffers are sized for
   int ntaps[4], nks[4], oy0[4], ox0[4];
   int tky[4][kMaxTapsX], tkx[4][kMaxTapsX];
   int tdy[4][kMaxTapsX], tdx[4][kMaxTapsX];
@@ -862,7 +792,6 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   // all-classes kernel (fvc_deconv_x3.hip) when two full-channel tile buffers fit in LDS; its pack
   // is this pack with one channel chunk. FVC_DX=0 keeps them on this kernel (at pack AND launch).
   c.dx = 0;
-  c.wl = 0;
   if (transposed && stride == 2 && c.nclass == 4 && fvc_env_int("FVC_DX", 1) &&
       (c.cinp == 64 || c.cinp == 96 || c.cinp == 128) && (c.ntp == 2 || c.ntp == 4)) {
     int maxt = 0;
@@ -879,7 +808,6 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
       c.nw = 8;
       c.wm = 2;
       c.wn = 2;
-      c.wnmax = 2;
       c.th = R;
       long long off = 0;
       for (int cl = 0; cl < 4; ++cl) {
@@ -897,29 +825,17 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   const int want_cc = fvc_env_int("FVC_X3_CC", 0);
   if ((want_cc == 8 || want_cc == 16 || want_cc == 32) && c.cinp % want_cc == 0) c.cc = want_cc;
   // block shape: 8 waves x 2 strips (16 output rows x 32 columns), 2 waves per SIMD;
-  // FVC_X3_NW / FVC_X3_WM override for experiments (WM=4 only with 4 waves)
+  // FVC_X3_WM=1 forces one strip per wave
   c.nw = 8;
   // stride-2 convs: one strip per wave (measured 0.22 vs 0.35 ms on the 544x960 128-channel layer:
   // two strips double the halo rows each staged chunk carries)
   c.wm = fvc_env_int("FVC_X3_WM", (!transposed && stride == 2) ? 1 : 2) == 1 ? 1 : 2;
-  // weight buffers in LDS (WL): two chunks of the block's fragments, sized for its widest N
-  c.wl = fvc_env_int("FVC_X3_WL", 0) ? 1 : 0;
-  c.wnmax = (c.wm == 1 && !transposed && stride == 2 && c.ntp % 4 == 0) ? 4 : (c.ntp >= 2 ? 2 : 1);
   // shrink the channel chunk, then the strips per wave, until two tile buffers fit in LDS
   for (;;) {
     c.th = c.nw * c.wm;
     const int ir = (c.th - 1) * c.sin + 1 + (c.dymax - c.dymin);
     const int ic = 31 * c.sin + 1 + (c.dxmax - c.dxmin);
-    size_t lds = 1024 + 2 * x3_tile_bytes(ir, ic, c.cc);
-    if (c.wl) {
-      int nkmax = 0;
-      for (int cl = 0; cl < c.nclass; ++cl) {
-        const int nk = fvc_cdiv(c.ntaps[cl] * (c.cc / 8), 2);
-        nkmax = nk > nkmax ? nk : nkmax;
-      }
-      lds += 2 * (size_t)nkmax * c.wnmax * kFrag * 16;
-    }
-    if (lds <= 160 * 1024) break;
+    if (1024 + 2 * x3_tile_bytes(ir, ic, c.cc) <= 160 * 1024) break;
     if (c.cc > 8 && c.cinp % (c.cc / 2) == 0) c.cc /= 2;
     else if (c.wm > 1) c.wm /= 2;
     else return false;
@@ -943,53 +859,52 @@ static int x3_kw(const float* w, size_t n) {
   return fvc_split_kw(mx);
 }
 
-template <int CC, int WM, int WN, int WG, int IOP, int POST, int NWV, int WL>
+template <int CC, int WM, int WN, int IOP, int POST, int NWV>
 static int x3_launch(const X3Args& a, dim3 grid, size_t lds, hipStream_t s) {
   if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)conv_x3_kernel<CC, WM, WN, WG, IOP, POST, NWV, WL>,
+    (void)hipFuncSetAttribute((const void*)conv_x3_kernel<CC, WM, WN, IOP, POST, NWV>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((conv_x3_kernel<CC, WM, WN, WG, IOP, POST, NWV, WL>), grid, dim3(NWV * 64), lds, s, a);
+  hipLaunchKernelGGL((conv_x3_kernel<CC, WM, WN, IOP, POST, NWV>), grid, dim3(NWV * 64), lds, s, a);
   FVC_CHECK_LAUNCH();
   return 0;
 }
 
 // exp after the epilogue is only ever taken with an untransformed input (Synthesis_prior_net
 // deconv3, synthesis_prior.py:25,57): instantiated for IN_NONE only
-template <int CC, int WM, int WN, int WG, int WL, int NWV = 8>
+template <int CC, int WM, int WN, int NWV = 8>
 static int x3_launch_iop(int iop, int post, const X3Args& a, dim3 grid, size_t lds, hipStream_t s) {
   if (post == kPostPool) {  // fused 2x2 pool epilogue: strip pairs per wave (run_x3)
-    if constexpr (WG == 1 && WL == 0 && WM == 2 && WN <= 2)
-      return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, WG, FVC_IN_NONE, kPostPool, NWV, WL>(a, grid, lds, s) : FVC_EINVAL;
+    if constexpr (WM == 2 && WN <= 2)
+      return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, FVC_IN_NONE, kPostPool, NWV>(a, grid, lds, s) : FVC_EINVAL;
     return FVC_EINVAL;
   }
   if (post == kPostTap) {  // fused tap epilogue: every output channel in one wave (run_x3)
-    if constexpr (WG == 1 && WL == 0 && ((WM == 2 && WN <= 2) || (WM == 1 && WN == 4)))
-      return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, WG, FVC_IN_NONE, kPostTap, NWV, WL>(a, grid, lds, s) : FVC_EINVAL;
+    if constexpr ((WM == 2 && WN <= 2) || (WM == 1 && WN == 4))
+      return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, FVC_IN_NONE, kPostTap, NWV>(a, grid, lds, s) : FVC_EINVAL;
     return FVC_EINVAL;
   }
   if (post == FVC_POST_EXP)
-    return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, WG, FVC_IN_NONE, FVC_POST_EXP, NWV, WL>(a, grid, lds, s) : FVC_EINVAL;
+    return iop == FVC_IN_NONE ? x3_launch<CC, WM, WN, FVC_IN_NONE, FVC_POST_EXP, NWV>(a, grid, lds, s) : FVC_EINVAL;
   switch (iop) {
-    case FVC_IN_NONE: return x3_launch<CC, WM, WN, WG, FVC_IN_NONE, FVC_POST_NONE, NWV, WL>(a, grid, lds, s);
-    case FVC_IN_RELU: return x3_launch<CC, WM, WN, WG, FVC_IN_RELU, FVC_POST_NONE, NWV, WL>(a, grid, lds, s);
-    case FVC_IN_ABS: return x3_launch<CC, WM, WN, WG, FVC_IN_ABS, FVC_POST_NONE, NWV, WL>(a, grid, lds, s);
-    case FVC_IN_ROUND: return x3_launch<CC, WM, WN, WG, FVC_IN_ROUND, FVC_POST_NONE, NWV, WL>(a, grid, lds, s);
+    case FVC_IN_NONE: return x3_launch<CC, WM, WN, FVC_IN_NONE, FVC_POST_NONE, NWV>(a, grid, lds, s);
+    case FVC_IN_RELU: return x3_launch<CC, WM, WN, FVC_IN_RELU, FVC_POST_NONE, NWV>(a, grid, lds, s);
+    case FVC_IN_ABS: return x3_launch<CC, WM, WN, FVC_IN_ABS, FVC_POST_NONE, NWV>(a, grid, lds, s);
+    case FVC_IN_ROUND: return x3_launch<CC, WM, WN, FVC_IN_ROUND, FVC_POST_NONE, NWV>(a, grid, lds, s);
   }
   return FVC_EINVAL;
 }
 
-// instantiated wave grids (8 waves, 2 per SIMD, <= 256 registers: scripts/kres.sh):
-// WG = 1 with WM, WN in {1, 2} or WM = 1, WN = 4; WG = 2 with WM = 4, WN = 1
-template <int CC, int WL>
-static int x3_launch_cc(int nwv, int wm, int wn, int wg, int iop, int post, const X3Args& a, dim3 grid,
-                        size_t lds, hipStream_t s) {
+// instantiated wave tiles (8 waves, 2 per SIMD, <= 256 registers: scripts/kres.sh):
+// WM, WN in {1, 2} or WM = 1, WN = 4
+template <int CC>
+static int x3_launch_cc(int nwv, int wm, int wn, int iop, int post, const X3Args& a, dim3 grid, size_t lds,
+                        hipStream_t s) {
   if (nwv != 8) return FVC_EINVAL;
-  if (wg == 2) return (wm == 4 && wn == 1 && !WL) ? x3_launch_iop<CC, 4, 1, 2, 0>(iop, post, a, grid, lds, s) : FVC_EINVAL;
-  if (wm == 2 && wn == 2) return x3_launch_iop<CC, 2, 2, 1, WL>(iop, post, a, grid, lds, s);
-  if (wm == 2 && wn == 1) return x3_launch_iop<CC, 2, 1, 1, WL>(iop, post, a, grid, lds, s);
-  if (wm == 1 && wn == 2) return x3_launch_iop<CC, 1, 2, 1, WL>(iop, post, a, grid, lds, s);
-  if (wm == 1 && wn == 1) return x3_launch_iop<CC, 1, 1, 1, WL>(iop, post, a, grid, lds, s);
-  if (wm == 1 && wn == 4) return x3_launch_iop<CC, 1, 4, 1, WL>(iop, post, a, grid, lds, s);
+  if (wm == 2 && wn == 2) return x3_launch_iop<CC, 2, 2>(iop, post, a, grid, lds, s);
+  if (wm == 2 && wn == 1) return x3_launch_iop<CC, 2, 1>(iop, post, a, grid, lds, s);
+  if (wm == 1 && wn == 2) return x3_launch_iop<CC, 1, 2>(iop, post, a, grid, lds, s);
+  if (wm == 1 && wn == 1) return x3_launch_iop<CC, 1, 1>(iop, post, a, grid, lds, s);
+  if (wm == 1 && wn == 4) return x3_launch_iop<CC, 1, 4>(iop, post, a, grid, lds, s);
   return FVC_EINVAL;
 }
 
@@ -1151,7 +1066,7 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   if (tw) {
     // every output channel in one wave: N-tiles 1, 2 (2 strips per wave) or 4 (1 strip); the
     // channel chunk (and so the weight pack) stays what x3_cfg chose: fewer strips only shrink LDS
-    if (post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.wl || c.ntp == 3 || c.ntp > 4 || pcp <= 0 ||
+    if (post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.ntp == 3 || c.ntp > 4 || pcp <= 0 ||
         pcp > 32 || (pcp & 3) || (c.dx && c.ntp != 4))
       return FVC_EINVAL;
     if (!c.dx) {
@@ -1162,8 +1077,7 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   }
   if (pool) {
     // y and avg_pool2d(y): stride-1 conv, two strips per wave (rows 2r, 2r + 1), one N-group
-    if (tw || transposed || stride != 1 || post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.wl || c.wm != 2 ||
-        c.ntp > 2)
+    if (tw || transposed || stride != 1 || post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.wm != 2 || c.ntp > 2)
       return FVC_EINVAL;
     post_op = kPostPool;
   }
@@ -1218,7 +1132,6 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   const int th = c.th;
   a.ir = (th - 1) * c.sin + 1 + (c.dymax - c.dymin);
   a.xcd = fvc_env_int("FVC_X3_XCD", 1) ? 1 : 0;
-  a.prio = fvc_env_int("FVC_X3_PRIO", 0) ? 1 : 0;
   a.ic = 31 * c.sin + 1 + (c.dxmax - c.dxmin);
   a.pt = c.pt;
   if (c.pt && (tw || pool)) return FVC_EINVAL;
@@ -1248,7 +1161,7 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
       }
       a.toff[cl][t] = off;
     }
-  size_t lds = 1024 + 2 * x3_tile_bytes(a.ir, a.ic, c.cc);
+  const size_t lds = 1024 + 2 * x3_tile_bytes(a.ir, a.ic, c.cc);
   const int tiles_x = fvc_cdiv(a.Wq, 32);
   const int tiles_y = fvc_cdiv(a.Hq, th);
   // N-tiles per block: 2 (each staged input element feeds 64 output channels) unless the layer
@@ -1263,47 +1176,20 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   if (!want_wn)
     while (wn > 1 && base * (c.ntp / wn) < 2LL * fvc_num_cus()) wn >>= 1;
   if ((tw || pool) && wn != c.ntp) return FVC_EINVAL;
-  // two N-groups of 4 waves x 4 strips instead of 8 waves x 2 strips x 2 N-tiles (same block
-  // tile: 16 rows x 32 pixels x 64 channels): each weight fragment feeds 4 strips
-  int wm = c.wm, wg = 1;
-  if (c.nw == 8 && !c.wl && !tw && !pool && fvc_env_int("FVC_X3_WG", 0) == 2 && c.wm == 2 && wn == 2) {
-    wm = 4;
-    wn = 1;
-    wg = 2;
-  }
-  const int nb = wn * wg;  // N-tiles per block
-  if (wn > c.wnmax && c.wl) return FVC_EINVAL;
-  a.wl_h = 0;
-  if (c.wl) {
-    int nkmax = 0;
-    for (int cl = 0; cl < c.nclass; ++cl) nkmax = c.nks[cl] > nkmax ? c.nks[cl] : nkmax;
-    a.wl_h = nkmax * wn * kFrag * 8;  // halves
-    lds += 2 * (size_t)a.wl_h * 2;
-  }
   if (lds > 160 * 1024) return FVC_EINVAL;
-  // persistent grid: ~one 8-wave block per CU (FVC_X3_BPC blocks per CU), each walking a
-  // contiguous run of spatial tiles
+  // persistent grid: ~one 8-wave block per CU, each walking a contiguous run of spatial tiles
   const int ncu = fvc_persistent_cus(cu_reserve);
-  const long long yz = (long long)(c.ntp / nb) * batch;
-  const int bpc = fvc_env_int("FVC_X3_BPC", 1);
-  long long gx = ((long long)ncu * bpc + yz - 1) / yz;  // blocks over all (tile, class) items
+  const long long yz = (long long)(c.ntp / wn) * batch;
+  long long gx = ((long long)ncu + yz - 1) / yz;  // blocks over all (tile, class) items
   if (gx > (long long)tiles_x * tiles_y * c.nclass) gx = (long long)tiles_x * tiles_y * c.nclass;
   if (gx < 1) gx = 1;
-  dim3 grid((unsigned)gx, c.ntp / nb, batch);
+  dim3 grid((unsigned)gx, c.ntp / wn, batch);
   // dynamic schedule when the caller's scratch holds the group counters (FVC_X3_DYN=0: static runs)
   a.sched = fvc_dyn_sched(sched, sched_len, 1 + (long long)grid.y * grid.z);
-  if (c.wl) {
-    switch (c.cc) {
-      case 8: return x3_launch_cc<8, 1>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
-      case 16: return x3_launch_cc<16, 1>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
-      case 32: return x3_launch_cc<32, 1>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
-    }
-    return FVC_EINVAL;
-  }
   switch (c.cc) {
-    case 8: return x3_launch_cc<8, 0>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
-    case 16: return x3_launch_cc<16, 0>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
-    case 32: return x3_launch_cc<32, 0>(c.nw, wm, wn, wg, in_op, post_op, a, grid, lds, s);
+    case 8: return x3_launch_cc<8>(c.nw, c.wm, wn, in_op, post_op, a, grid, lds, s);
+    case 16: return x3_launch_cc<16>(c.nw, c.wm, wn, in_op, post_op, a, grid, lds, s);
+    case 32: return x3_launch_cc<32>(c.nw, c.wm, wn, in_op, post_op, a, grid, lds, s);
   }
   return FVC_EINVAL;
 }
@@ -1447,7 +1333,7 @@ int fvc_x3_tap_pack_weight(const float* w, void* wp, float* osc_out, int np, int
 
 int fvc_conv_x3_tap_supported(int cin, int cout, int ksize, int stride, int transposed, int pcp) {
   X3Cfg c;
-  if (!x3_cfg(cin, cout, ksize, stride, transposed, c) || c.wl || c.pt || pcp <= 0 || pcp > 32 || (pcp & 3)) return 0;
+  if (!x3_cfg(cin, cout, ksize, stride, transposed, c) || c.pt || pcp <= 0 || pcp > 32 || (pcp & 3)) return 0;
   if (c.dx) return c.ntp == 4;  // the all-classes kernel's tap form: 1 strip x 4 N-tiles
   const int wm = c.ntp == 4 ? 1 : c.wm;
   return (wm == 2 && c.ntp <= 2) || (wm == 1 && c.ntp == 4);
@@ -1477,7 +1363,7 @@ int fvc_deconv2d_nhwc_x3_tap(const float* x, const void* wpack, float osc, const
 
 int fvc_conv_x3_pool_supported(int cin, int cout, int ksize) {
   X3Cfg c;
-  return x3_cfg(cin, cout, ksize, 1, 0, c) && !c.wl && !c.pt && c.wm == 2 && c.ntp <= 2;
+  return x3_cfg(cin, cout, ksize, 1, 0, c) && !c.pt && c.wm == 2 && c.ntp <= 2;
 }
 
 int fvc_conv2d_nhwc_x3_pool(const float* x, const void* wpack, float osc, const float* bias, const float* res,

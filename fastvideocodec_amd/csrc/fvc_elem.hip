@@ -5,7 +5,6 @@
 // contraction off (no FMA fusion) and in the reference's operand order, so results track the
 // CPU path to ~1 ulp.
 #include "fvc_common.h"
-#include <stdlib.h>
 #include "fvc_dist.h"
 #include <string.h>
 
@@ -130,16 +129,19 @@ __device__ __forceinline__ void stage_p_window(const float* __restrict__ Pb, int
   }
 }
 
+// Output rows per block of the LDS tap gathers below (x 32 columns).
+constexpr int kGatherTH = 8;
+
 // Stride-1 3x3 tap gather through LDS (the second half of the fused producer + tap path): a block
-// stages the P tile of its 16 x 32 outputs plus a 1-pixel halo with coalesced 16-B loads (zeros
+// stages the P tile of its 8 x 32 outputs plus a 1-pixel halo with coalesced 16-B loads (zeros
 // outside the image), pixel stride pcp + 1 words so the per-tap reads of consecutive outputs hit
 // distinct banks, then sums bias + taps in k_tap_gather's order (an out-of-image tap adds +0).
-template <int COUT, int TH>
+template <int COUT>
 __global__ __launch_bounds__(256) void k_tap_gather3_lds(const float* __restrict__ P, int pcp,
                                                          const float* __restrict__ bias,
                                                          const float* __restrict__ res, float* __restrict__ y,
                                                          int H, int W, float act_slope, int post_op) {
-  constexpr int TW = 32, IR = TH + 2, IC = TW + 2;
+  constexpr int TH = kGatherTH, TW = 32, IR = TH + 2, IC = TW + 2;
   extern __shared__ float sp[];
   const int ps = pcp + 1;
   const size_t b = blockIdx.z;
@@ -180,16 +182,16 @@ __global__ __launch_bounds__(256) void k_tap_gather3_lds(const float* __restrict
   }
 }
 
-// Transposed (stride 2, output padding 1) tap gather through LDS: a block's 16 x 32 outputs read
-// input rows Y0/2 - 1 .. Y0/2 + 8 and columns X0/2 - 1 .. X0/2 + 17 of P (k = 3 or 5), staged
+// Transposed (stride 2, output padding 1) tap gather through LDS: a block's 8 x 32 outputs read
+// input rows Y0/2 - 1 .. Y0/2 + 4 and columns X0/2 - 1 .. X0/2 + 17 of P (k = 3 or 5), staged
 // once with coalesced 16-B loads; per output the same tap order as k_tap_gather.
-template <int KS, int COUT, int TH>
+template <int KS, int COUT>
 __global__ __launch_bounds__(256) void k_tap_gather_t2_lds(const float* __restrict__ P, int pcp,
                                                            const float* __restrict__ bias,
                                                            const float* __restrict__ res, float* __restrict__ y,
                                                            int H, int W, float act_slope, int post_op) {
   // output rows Y0 .. Y0 + TH - 1 read input rows Y0/2 - 1 .. Y0/2 + TH/2 (k <= 5)
-  constexpr int TW = 32, IR = TH / 2 + 2, IC = 19, pad = KS / 2;
+  constexpr int TH = kGatherTH, TW = 32, IR = TH / 2 + 2, IC = 19, pad = KS / 2;
   extern __shared__ float sp[];
   const int ps = pcp + 1;
   const int Ho = 2 * H, Wo = 2 * W;
@@ -408,42 +410,9 @@ __device__ __forceinline__ unsigned udiv_magic(unsigned n, unsigned d, unsigned 
   return q * d > n ? q - 1 : q;
 }
 
-__global__ void k_up2_add_q16(const float* __restrict__ src, const float* __restrict__ skip, float* __restrict__ out,
-                              int B, int h, int w, int ac, float scale, unsigned mW, unsigned mH, float usy, float usx) {
-  const unsigned H = 2u * h, W = 2u * w;
-  const unsigned n = (unsigned)B * H * W * 16u;
-  const float4* s4 = reinterpret_cast<const float4*>(src);
-  for (unsigned e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-    const unsigned c4 = e & 15u;
-    const unsigned p = e >> 4;
-    const unsigned row = udiv_magic(p, W, mW);
-    const int x = (int)(p - row * W);
-    const unsigned b = udiv_magic(row, H, mH);
-    const int y = (int)(row - b * H);
-    const UpIdx uy = up2_index(y, h, (int)H, ac, usy), ux = up2_index(x, w, (int)W, ac, usx);
-    const unsigned bb = b * (unsigned)h * (unsigned)w;
-    const float4 a = s4[(bb + (unsigned)uy.i0 * w + ux.i0) * 16u + c4];
-    const float4 bq = s4[(bb + (unsigned)uy.i0 * w + ux.i1) * 16u + c4];
-    const float4 c = s4[(bb + (unsigned)uy.i1 * w + ux.i0) * 16u + c4];
-    const float4 d = s4[(bb + (unsigned)uy.i1 * w + ux.i1) * 16u + c4];
-    float4 v;
-    v.x = fvc_lerp2d(a.x, bq.x, c.x, d.x, ux.l0, ux.l1, uy.l0, uy.l1);
-    v.y = fvc_lerp2d(a.y, bq.y, c.y, d.y, ux.l0, ux.l1, uy.l0, uy.l1);
-    v.z = fvc_lerp2d(a.z, bq.z, c.z, d.z, ux.l0, ux.l1, uy.l0, uy.l1);
-    v.w = fvc_lerp2d(a.w, bq.w, c.w, d.w, ux.l0, ux.l1, uy.l0, uy.l1);
-    if (scale != 1.f) { v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale; }
-    if (skip) {
-      const float4 sk = reinterpret_cast<const float4*>(skip)[e];
-      v.x = sk.x + v.x; v.y = sk.y + v.y; v.z = sk.z + v.z; v.w = sk.w + v.w;
-    }
-    reinterpret_cast<float4*>(out)[e] = v;
-  }
-}
-
 // NE elements per thread per iteration (e, e + stride, ...), all loads issued before the stores:
-// more independent loads in flight per wave than the one-element loop (as k_mc_assemble_q); NT:
-// the skip tensor by non-temporal loads (it is read once)
-template <bool NT>
+// more independent loads in flight per wave than a one-element loop (as k_mc_assemble_q); the skip
+// tensor by non-temporal loads (it is read once)
 __device__ __forceinline__ float4 up2_q16_elem(const float4* __restrict__ s4, const float* __restrict__ skip,
                                                unsigned e, unsigned H, unsigned W, int h, int w, int ac, float scale,
                                                unsigned mW, unsigned mH, float usy, float usx) {
@@ -466,20 +435,15 @@ __device__ __forceinline__ float4 up2_q16_elem(const float4* __restrict__ s4, co
   v.w = fvc_lerp2d(a.w, bq.w, c.w, d.w, ux.l0, ux.l1, uy.l0, uy.l1);
   if (scale != 1.f) { v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale; }
   if (skip) {
-    float4 sk;
-    if constexpr (NT) {
-      const float* q = skip + 4 * (size_t)e;
-      sk = make_float4(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2),
-                       __builtin_nontemporal_load(q + 3));
-    } else {
-      sk = reinterpret_cast<const float4*>(skip)[e];
-    }
+    const float* q = skip + 4 * (size_t)e;
+    const float4 sk = make_float4(__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1),
+                                  __builtin_nontemporal_load(q + 2), __builtin_nontemporal_load(q + 3));
     v.x = sk.x + v.x; v.y = sk.y + v.y; v.z = sk.z + v.z; v.w = sk.w + v.w;
   }
   return v;
 }
 
-template <int NE, bool NT>
+template <int NE>
 __global__ void k_up2_add_q16p(const float* __restrict__ src, const float* __restrict__ skip, float* __restrict__ out,
                                int B, int h, int w, int ac, float scale, unsigned mW, unsigned mH, float usy,
                                float usx) {
@@ -493,7 +457,7 @@ __global__ void k_up2_add_q16p(const float* __restrict__ src, const float* __res
 #pragma unroll
     for (int k = 0; k < NE; ++k) {
       ei[k] = e + k * st < n ? e + k * st : e;
-      v[k] = up2_q16_elem<NT>(s4, skip, ei[k], H, W, h, w, ac, scale, mW, mH, usy, usx);
+      v[k] = up2_q16_elem(s4, skip, ei[k], H, W, h, w, ac, scale, mW, mH, usy, usx);
     }
 #pragma unroll
     for (int k = 0; k < NE; ++k) reinterpret_cast<float4*>(out)[ei[k]] = v[k];
@@ -1407,11 +1371,6 @@ __global__ __launch_bounds__(kBlk) void k_gc_forward(const float* __restrict__ x
   block_reduce_store<1>(acc, ws);
 }
 
-static int env_flag(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
 static int grid_for(size_t n) {
   size_t g = (n + kBlk - 1) / kBlk;
   if (g > 8192) g = 8192;
@@ -1481,21 +1440,14 @@ int fvc_upsample2x_add_nhwc(const float* src, const float* skip, float* out, int
   // align_corners scales (in - 1) / (out - 1), one host float division each (as ATen's CPU kernel)
   const float usy = H2 > 1 ? (float)(h - 1) / (float)(H2 - 1) : 0.f;
   const float usx = W2 > 1 ? (float)(w - 1) / (float)(W2 - 1) : 0.f;
-  if (cp == 64 && (unsigned long long)batch * H2 * W2 * 16ull < (1ull << 32) && env_flag("FVC_UP2_Q16", 1)) {
+  // 64 channels: two elements per thread with 32-bit indexes (e + 2 * stride stays below 2^32:
+  // stride <= 8192 * kBlk, 2 * stride < 2^24), the skip tensor (read once: c0 / c1 are dead after this add) by
+  // non-temporal loads: 1088x1920x64 at 8 frames 2.16 -> 1.99 ms (profiles/r5/up2_pair); same bits
+  // as the generic kernel, which FVC_UP2_Q16=0 selects
+  if (cp == 64 && n + (1ull << 24) < (1ull << 32) && fvc_env_int("FVC_UP2_Q16", 1)) {
     const unsigned mW = (unsigned)(((1ull << 32) + W2 - 1) / W2), mH = (unsigned)(((1ull << 32) + H2 - 1) / H2);
-    // (index arithmetic e + 2 * stride stays below 2^32: stride <= 8192 * kBlk)
-    // two elements per thread, the skip tensor (read once: c0 / c1 are dead after this add) by
-    // non-temporal loads: 1088x1920x64 at 8 frames 2.16 -> 1.99 ms (profiles/r5/up2_pair); same bits
-    const bool nt = env_flag("FVC_UP2_NT", 1) != 0;
-    if (n + (1ull << 24) < (1ull << 32) && env_flag("FVC_UP2_PAIR", 1) && nt)
-      hipLaunchKernelGGL((k_up2_add_q16p<2, true>), dim3(grid_for((n + 1) / 2)), dim3(kBlk), 0, (hipStream_t)s, src, skip,
-                         out, batch, h, w, align_corners, scale, mW, mH, usy, usx);
-    else if (n + (1ull << 24) < (1ull << 32) && env_flag("FVC_UP2_PAIR", 1))
-      hipLaunchKernelGGL((k_up2_add_q16p<2, false>), dim3(grid_for((n + 1) / 2)), dim3(kBlk), 0, (hipStream_t)s, src, skip,
-                         out, batch, h, w, align_corners, scale, mW, mH, usy, usx);
-    else
-      hipLaunchKernelGGL(k_up2_add_q16, dim3(grid_for(n)), dim3(kBlk), 0, (hipStream_t)s, src, skip, out, batch, h, w,
-                         align_corners, scale, mW, mH, usy, usx);
+    hipLaunchKernelGGL((k_up2_add_q16p<2>), dim3(grid_for((n + 1) / 2)), dim3(kBlk), 0, (hipStream_t)s, src, skip, out,
+                       batch, h, w, align_corners, scale, mW, mH, usy, usx);
   } else {
     hipLaunchKernelGGL(k_up2_add, dim3(grid_for(n)), dim3(kBlk), 0, (hipStream_t)s, src, skip, out, batch, h, w, cp,
                        align_corners, scale, usy, usx);
@@ -1508,7 +1460,7 @@ int fvc_spynet_assemble(const float* im1, const float* im2, const float* flow_pr
                         int batch, int h, int w, fvc_stream_t s) {
   if (!im1 || !im2 || !flow_up || !x8 || (h & 1) || (w & 1) || h < 2 || w < 2) return FVC_EINVAL;
   const size_t n = (size_t)batch * h * w;
-  if (2ull * n < (1ull << 32) && env_flag("FVC_ASSEMBLE_Q", 1)) {
+  if (2ull * n < (1ull << 32) && fvc_env_int("FVC_ASSEMBLE_Q", 1)) {
     // two pixels per thread per iteration: half as many threads as pixels
     const unsigned mW = (unsigned)(((1ull << 32) + w - 1) / w), mH = (unsigned)(((1ull << 32) + h - 1) / h);
     hipLaunchKernelGGL(k_spynet_assemble_q, dim3(grid_for((n + 1) / 2)), dim3(kBlk), 0, (hipStream_t)s, im1, im2, flow_prev,
@@ -1525,7 +1477,7 @@ int fvc_mc_assemble(const float* ref, const float* mv, float* warpframe, float* 
                     fvc_stream_t s) {
   if (!ref || !mv || !warpframe || !x8 || h < 2 || w < 2) return FVC_EINVAL;
   const size_t n = (size_t)batch * h * w;
-  if (2ull * n < (1ull << 32) && env_flag("FVC_ASSEMBLE_Q", 1)) {
+  if (2ull * n < (1ull << 32) && fvc_env_int("FVC_ASSEMBLE_Q", 1)) {
     const unsigned mW = (unsigned)(((1ull << 32) + w - 1) / w), mH = (unsigned)(((1ull << 32) + h - 1) / h);
     hipLaunchKernelGGL(k_mc_assemble_q, dim3(grid_for((n + 1) / 2)), dim3(kBlk), 0, (hipStream_t)s, ref, mv, warpframe, x8,
                        batch, h, w, mW, mH);
@@ -1550,41 +1502,32 @@ int fvc_tap_gather_nhwc(const float* P, int pcp, const float* bias, const float*
   const dim3 g(grid_for(n)), bl(kBlk);
   hipStream_t st = (hipStream_t)s;
   if (!transposed && ksize == 3 && pcp <= 32) {
-    // 8-row tiles: 39 KB of LDS at pcp 28, four blocks per CU (FVC_GATHER_TH=16: 18-row halo tiles)
-    const char* th_env = getenv("FVC_GATHER_TH");
-    const int th = (th_env && atoi(th_env) == 16) ? 16 : 8;
-    const dim3 gt(fvc_cdiv(w, 32), fvc_cdiv(h, th), batch);
-    const size_t lds = (size_t)(th + 2) * 34 * (pcp + 1) * 4;
-#define FVC_TGL(CO, TH)                                                                                         \
-    if (cout == CO && th == TH) {                                                                             \
+    // 8-row tiles: 39 KB of LDS at pcp 28, four blocks per CU
+    const dim3 gt(fvc_cdiv(w, 32), fvc_cdiv(h, kGatherTH), batch);
+    const size_t lds = (size_t)(kGatherTH + 2) * 34 * (pcp + 1) * 4;
+#define FVC_TGL(CO)                                                                                            \
+    if (cout == CO) {                                                                                         \
       if (lds > 64 * 1024)                                                                                    \
-        (void)hipFuncSetAttribute((const void*)k_tap_gather3_lds<CO, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+        (void)hipFuncSetAttribute((const void*)k_tap_gather3_lds<CO>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                   (int)lds);                                                                  \
-      hipLaunchKernelGGL((k_tap_gather3_lds<CO, TH>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, post_op); \
+      hipLaunchKernelGGL((k_tap_gather3_lds<CO>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, post_op); \
       FVC_CHECK_LAUNCH();                                                                                     \
       return 0;                                                                                               \
     }
-    FVC_TGL(1, 8) FVC_TGL(2, 8) FVC_TGL(3, 8) FVC_TGL(4, 8)
-    FVC_TGL(1, 16) FVC_TGL(2, 16) FVC_TGL(3, 16) FVC_TGL(4, 16)
+    FVC_TGL(1) FVC_TGL(2) FVC_TGL(3) FVC_TGL(4)
 #undef FVC_TGL
   }
   if (transposed && pcp <= 128) {
-    // 8-row output tiles (6 x 19 input pixels in LDS: ~35 KB at pcp 76, four blocks per CU);
-    // FVC_GATHER_TH=16: 16-row tiles
-    const char* th_env = getenv("FVC_GATHER_TH");
-    const int th = (th_env && atoi(th_env) == 16) ? 16 : 8;
-    const dim3 gt(fvc_cdiv(Wo, 32), fvc_cdiv(Ho, th), batch);
-    const size_t lds = (size_t)(th / 2 + 2) * 19 * (pcp + 1) * 4;
+    // 8-row output tiles (6 x 19 input pixels in LDS: ~35 KB at pcp 76, four blocks per CU)
+    const dim3 gt(fvc_cdiv(Wo, 32), fvc_cdiv(Ho, kGatherTH), batch);
+    const size_t lds = (size_t)(kGatherTH / 2 + 2) * 19 * (pcp + 1) * 4;
 #define FVC_TGT(KS, CO)                                                                                        \
     if (ksize == KS && cout == CO) {                                                                          \
-      const void* fn = th == 8 ? (const void*)k_tap_gather_t2_lds<KS, CO, 8> : (const void*)k_tap_gather_t2_lds<KS, CO, 16>; \
-      if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      if (th == 8)                                                                                            \
-        hipLaunchKernelGGL((k_tap_gather_t2_lds<KS, CO, 8>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, \
-                           slope, post_op);                                                                   \
-      else                                                                                                    \
-        hipLaunchKernelGGL((k_tap_gather_t2_lds<KS, CO, 16>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, \
-                           slope, post_op);                                                                   \
+      if (lds > 64 * 1024)                                                                                    \
+        (void)hipFuncSetAttribute((const void*)k_tap_gather_t2_lds<KS, CO>,                                   \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
+      hipLaunchKernelGGL((k_tap_gather_t2_lds<KS, CO>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, \
+                         post_op);                                                                            \
       FVC_CHECK_LAUNCH();                                                                                     \
       return 0;                                                                                               \
     }
@@ -1671,7 +1614,7 @@ int fvc_gc_forward(const float* x, const float* scale, const float* mu, float* x
 
 // persistent grid of the split-precision GDN kernels: 4 groups of 32 pixels per block and pass
 static unsigned gdn_x3_blocks(size_t npix) {
-  static const int cap = env_flag("FVC_GDN_BLOCKS", 1024);
+  static const int cap = fvc_env_int("FVC_GDN_BLOCKS", 1024);
   size_t nb = ((npix + 31) / 32 + 3) / 4;
   if (nb > (size_t)cap) nb = (size_t)cap;
   return nb < 1 ? 1u : (unsigned)nb;
@@ -1681,7 +1624,7 @@ int fvc_gdn_nhwc(const float* x, float* y, const float* beta, const float* gamma
                  int inverse, fvc_stream_t s) {
   if (!x || !y || !beta || !gamma || c != 64) return FVC_EINVAL;
   const size_t npix = (size_t)batch * h * w;
-  if (env_flag("FVC_GDN_X3", 1)) {
+  if (fvc_env_int("FVC_GDN_X3", 1)) {
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (inverse)
       hipLaunchKernelGGL((k_gdn_x3<0, true>), dim3(gdn_x3_blocks(npix)), dim3(256), 0, (hipStream_t)s, x, y, beta, gamma,
@@ -1715,7 +1658,7 @@ int fvc_gdn_tap_nhwc(const float* x, float* P, const float* beta, const float* g
   for (int i = 0; i < ntiles; ++i) t[i] = tap_osc[i];
   const float4 tosc = make_float4(t[0], t[1], t[2], t[3]);
   const uint4* tw = (const uint4*)tap_wpack;
-  if (env_flag("FVC_GDN_X3", 1)) {
+  if (fvc_env_int("FVC_GDN_X3", 1)) {
     const unsigned nb = gdn_x3_blocks(npix);
 #define FVC_GX(N, I)                                                                                           \
   if (ntiles == N && !!inverse == I)                                                                           \

@@ -11,7 +11,6 @@
 #pragma once
 #include "fvc_common.h"
 #include <math.h>
-#include <stdlib.h>
 
 // cache policy of the activation stores (aux operand of buffer_store; experiment builds only,
 // e.g. 2 = non-temporal on gfx950)
@@ -141,11 +140,6 @@ __device__ __forceinline__ void mfma3(f32x4& acc, f32x4& cor, const h8& uh, cons
 }  // namespace fvc_split
 
 // ------------------------------------------------------------------------------------ host side
-static inline int fvc_env_int(const char* n, int dflt) {
-  const char* v = getenv(n);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
 // CUs of the current device, queried once per process (hidden, not static: one cache for the
 // whole library)
 __attribute__((visibility("hidden"))) inline int fvc_num_cus() {

@@ -267,9 +267,8 @@ def x3_dispatches(batch, y_image_bytes, res_image_bytes=0):
 
 # every environment switch the split-precision conv sources read (fvc_conv_x3.hip, fvc_deconv_x3.hip,
 # fvc_conv_wino.hip): a pack's layout id is re-queried only when one of them changes
-_LAYOUT_ENV = ("FVC_DX", "FVC_DX_PAIR", "FVC_X3_BPC", "FVC_X3_CC", "FVC_X3_CIN4", "FVC_X3_DYN", "FVC_X3_PRIO",
-               "FVC_X3_PT", "FVC_X3_RESERVE", "FVC_X3_SMALLN", "FVC_X3_SPLIT_BYTES", "FVC_X3_WG", "FVC_X3_WL",
-               "FVC_X3_WM", "FVC_X3_WN", "FVC_X3_XCD")
+_LAYOUT_ENV = ("FVC_DX", "FVC_DX_PAIR", "FVC_X3_CC", "FVC_X3_CIN4", "FVC_X3_DYN", "FVC_X3_PT", "FVC_X3_RESERVE",
+               "FVC_X3_SMALLN", "FVC_X3_SPLIT_BYTES", "FVC_X3_WM", "FVC_X3_WN", "FVC_X3_XCD")
 
 
 def _layout_env():
