@@ -20,7 +20,7 @@ OUT = os.path.join(HERE, "libfvc.so")
 OBJDIR = os.path.join(HERE, "build")
 HEADERS = [os.path.join(HERE, "csrc", "fvc_common.h"), os.path.join(HERE, "csrc", "fvc_dist.h"),
            os.path.join(HERE, "csrc", "fvc_dx.h"), os.path.join(HERE, "csrc", "fvc_split.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fvc.h")]
+           os.path.join(HERE, "csrc", "fvc_taps.h"), os.path.join(os.path.dirname(HERE), "include", "fvc.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

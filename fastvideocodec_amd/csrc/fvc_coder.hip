@@ -734,17 +734,11 @@ int fvc_rans_decode(const uint32_t* packed, const int64_t* pack_off, const int32
     return FVC_EINVAL;
   const uint32_t* img_off = (const uint32_t*)lut;
   if (streams_per_block < 0 || streams_per_block > 64) return FVC_EINVAL;
-  // kDec2Lds (static_assert'ed against gfx950's 160 KB per CU above) needs the opt-in: a device
-  // that refuses it cannot run this kernel, so report that instead of a generic launch failure
-  const hipError_t attr =
-      hipFuncSetAttribute((const void*)k_rans_decode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDec2Lds);
-  if (attr != hipSuccess) return -(int)attr;
   const int spb = streams_per_block ? streams_per_block : kDecSpb;
-  hipLaunchKernelGGL(k_rans_decode, dim3((nstreams + spb - 1) / spb), dim3(128), kDec2Lds, (hipStream_t)s, packed,
-                     pack_off, indexes, sym_off, nstreams, cdf_sizes, offsets, ntables, img_off, img_off + ntables + 1,
-                     symbols, status, spb);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  // kDec2Lds (static_assert'ed against gfx950's 160 KB per CU above) needs the opt-in fvc_launch makes
+  return fvc_launch(k_rans_decode, dim3((nstreams + spb - 1) / spb), dim3(128), kDec2Lds, (hipStream_t)s, packed,
+                    pack_off, indexes, sym_off, nstreams, cdf_sizes, offsets, ntables, img_off, img_off + ntables + 1,
+                    symbols, status, spb);
 }
 
 }  // extern "C"

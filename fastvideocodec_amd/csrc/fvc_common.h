@@ -11,6 +11,20 @@
     if (e__ != hipSuccess) return -(int)e__;                 \
   } while (0)
 
+// Launch a kernel with `lds` bytes of dynamic LDS: more than the default limit of 64 KB is opted
+// into first (a device that refuses it reports that error instead of a failed launch).
+// Returns 0 or -(hipError_t).
+template <typename... P, typename... A>
+static inline int fvc_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(int)e;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+  FVC_CHECK_LAUNCH();
+  return 0;
+}
+
 static inline int fvc_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int fvc_rup(int a, int b) { return fvc_cdiv(a, b) * b; }
 

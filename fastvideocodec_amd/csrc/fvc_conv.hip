@@ -22,6 +22,7 @@
 //    the input with a subset of taps (blockIdx.z = batch*classes + class); no zero-insertion.
 //  * epilogue: bias, activation (ReLU / LeakyReLU 0.1), residual add, exp; pad channels = 0.
 #include "fvc_common.h"
+#include "fvc_taps.h"
 
 namespace {
 
@@ -552,70 +553,21 @@ __global__ __launch_bounds__(kThreads) void conv_smalln_f32_kernel(const ConvArg
 }
 
 // ------------------------------------------------------------------ host-side geometry
-struct Cfg {
-  int cinp, coutp, ntp, cc, wm, wn, nclass, nchunks, smalln, sn_py, th, pipe, lds_bufs;
-  int sin, sout;
-  int ntaps[4], kbc[4], oy0[4], ox0[4];
-  int tky[4][kMaxTaps], tkx[4][kMaxTaps];  // kernel tap (ky,kx)
-  int tdy[4][kMaxTaps], tdx[4][kMaxTaps];  // input offsets
-  int dymin, dymax, dxmin, dxmax;
-  int gy0[4], gny[4], gx0[4], gnx[4];
+struct Cfg : FvcTaps {
+  int cinp, coutp, ntp, cc, wm, wn, nchunks, smalln, sn_py, th, pipe, lds_bufs;
+  int kbc[4];
+  int gy0[4], gny[4], gx0[4], gnx[4];  // per class: the tap grid (first offset, extent)
   long long wcls[4];
   long long wtotal;
 };
-
-static int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
+static_assert(kMaxTaps == kFvcMaxTaps, "ConvArgs and FvcTaps hold the same tap lists");
 
 static bool make_cfg(int cin, int cout, int ks, int stride, int transposed, Cfg& c) {
-  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3 && ks != 5 && ks != 7) || (stride != 1 && stride != 2))
-    return false;
+  if (cin <= 0 || cout <= 0 || !fvc_taps(ks, stride, transposed, 0, c)) return false;
   c.cinp = fvc_rup(cin, 4);
   c.coutp = fvc_rup(cout, 4);
   c.ntp = fvc_cdiv(c.coutp, 32);
   if (c.ntp > 4) return false;
-  const int pad = ks / 2;
-  if (!transposed) {
-    c.nclass = 1;
-    c.sin = stride;
-    c.sout = 1;
-    c.ntaps[0] = 0;
-    for (int ky = 0; ky < ks; ++ky)
-      for (int kx = 0; kx < ks; ++kx) {
-        int t = c.ntaps[0]++;
-        c.tky[0][t] = ky; c.tkx[0][t] = kx;
-        c.tdy[0][t] = ky - pad; c.tdx[0][t] = kx - pad;
-      }
-    c.oy0[0] = c.ox0[0] = 0;
-  } else {
-    c.nclass = stride * stride;
-    c.sin = 1;
-    c.sout = stride;
-    for (int py = 0; py < stride; ++py)
-      for (int px = 0; px < stride; ++px) {
-        const int cl = py * stride + px;
-        c.ntaps[cl] = 0;
-        c.oy0[cl] = py; c.ox0[cl] = px;
-        for (int ky = 0; ky < ks; ++ky) {
-          if (((py + pad - ky) % stride + stride) % stride) continue;
-          for (int kx = 0; kx < ks; ++kx) {
-            if (((px + pad - kx) % stride + stride) % stride) continue;
-            int t = c.ntaps[cl]++;
-            c.tky[cl][t] = ky; c.tkx[cl][t] = kx;
-            c.tdy[cl][t] = floordiv(py + pad - ky, stride);
-            c.tdx[cl][t] = floordiv(px + pad - kx, stride);
-          }
-        }
-      }
-  }
-  c.dymin = c.dxmin = 1 << 20;
-  c.dymax = c.dxmax = -(1 << 20);
-  for (int cl = 0; cl < c.nclass; ++cl)
-    for (int t = 0; t < c.ntaps[cl]; ++t) {
-      c.dymin = c.tdy[cl][t] < c.dymin ? c.tdy[cl][t] : c.dymin;
-      c.dymax = c.tdy[cl][t] > c.dymax ? c.tdy[cl][t] : c.dymax;
-      c.dxmin = c.tdx[cl][t] < c.dxmin ? c.tdx[cl][t] : c.dxmin;
-      c.dxmax = c.tdx[cl][t] > c.dxmax ? c.tdx[cl][t] : c.dxmax;
-    }
   for (int cl = 0; cl < c.nclass; ++cl) {
     int y0 = 1 << 20, y1 = -(1 << 20), x0 = 1 << 20, x1 = -(1 << 20);
     for (int t = 0; t < c.ntaps[cl]; ++t) {
@@ -677,9 +629,7 @@ static bool make_cfg(int cin, int cout, int ks, int stride, int transposed, Cfg&
 
 template <int CC, int WM, int WN>
 static int launch_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((conv_mfma_f32_kernel<CC, WM, WN>), grid, dim3(kThreads), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_mfma_f32_kernel<CC, WM, WN>, grid, dim3(kThreads), lds, s, a);
 }
 
 template <int CC, int WM>
@@ -701,19 +651,8 @@ static int launch_wm(int wm, int wn, const ConvArgs& a, dim3 grid, size_t lds, h
 
 template <int CC, int COUT, int KMAX>
 static int launch_sn_t(int py, const ConvArgs& a, dim3 grid, dim3 blk, size_t lds, hipStream_t s) {
-  if (py == 2) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)conv_smalln_f32_kernel<CC, COUT, KMAX, 2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_smalln_f32_kernel<CC, COUT, KMAX, 2>), grid, blk, lds, s, a);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)conv_smalln_f32_kernel<CC, COUT, KMAX, 4>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((conv_smalln_f32_kernel<CC, COUT, KMAX, 4>), grid, blk, lds, s, a);
-  }
-  FVC_CHECK_LAUNCH();
-  return 0;
+  if (py == 2) return fvc_launch(conv_smalln_f32_kernel<CC, COUT, KMAX, 2>, grid, blk, lds, s, a);
+  return fvc_launch(conv_smalln_f32_kernel<CC, COUT, KMAX, 4>, grid, blk, lds, s, a);
 }
 
 template <int CC, int COUT>
@@ -737,11 +676,7 @@ static int launch_sn_n(int cout, int kmax, int py, const ConvArgs& a, dim3 grid,
 
 template <int CC, int WN>
 static int launch_pp_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)conv_mfma_pipe_kernel<CC, 2, WN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((conv_mfma_pipe_kernel<CC, 2, WN>), grid, dim3(kPipeWaves * 64), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_mfma_pipe_kernel<CC, 2, WN>, grid, dim3(kPipeWaves * 64), lds, s, a);
 }
 
 template <int CC>
@@ -780,19 +715,12 @@ static int run_conv(const float* x, const float* wpack, const float* bias, const
                     int transposed, int in_op, int act, int post_op, hipStream_t s) {
   Cfg c;
   if (!make_cfg(cin, cout, ks, stride, transposed, c)) return FVC_EINVAL;
-  if (!x || !wpack || !bias || !y || batch <= 0 || h <= 0 || w <= 0) return FVC_EINVAL;
+  if (!x || !wpack || !bias || !y || batch <= 0) return FVC_EINVAL;
   ConvArgs a;
   a.x = x; a.w = wpack; a.bias = bias; a.res = res; a.y = y;
   a.B = batch; a.H = h; a.W = w; a.cinp = c.cinp;
   a.coutp = c.coutp; a.cout = cout;
-  if (!transposed) {
-    if (stride == 2 && ((h & 1) || (w & 1))) return FVC_EINVAL;
-    a.Ho = h / stride; a.Wo = w / stride;
-    a.Hq = a.Ho; a.Wq = a.Wo;
-  } else {
-    a.Ho = h * stride; a.Wo = w * stride;
-    a.Hq = h; a.Wq = w;
-  }
+  if (!fvc_out_dims(h, w, stride, transposed, a.Ho, a.Wo, a.Hq, a.Wq)) return FVC_EINVAL;
   a.sin = c.sin; a.sout = c.sout; a.nclass = c.nclass; a.nchunks = c.nchunks; a.ntp = c.ntp;
   a.dymin = c.dymin; a.dxmin = c.dxmin;
   const int TH = c.th;

@@ -265,9 +265,6 @@ int stem_launch(StemArgs a, hipStream_t st) {
   const size_t lds = (size_t)G::kSteps * NT * 2 * 64 * 16 + 32 * NT * 4 + 2 * 2 * (size_t)T::kPlane;
   static_assert((size_t)G::kSteps * NT * 2 * 64 * 16 + 32 * NT * 4 + 4 * (size_t)T::kPlane <= 160 * 1024,
                 "stem LDS over 160 KB");
-  const hipError_t e = hipFuncSetAttribute((const void*)conv_stem_kernel<CINP, NT, K, S, ACT, NW>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return -(int)e;
   // persistent: as many blocks as fit on every CU at once (3-4 per CU: 12-16 waves keep the store
   // stream full), strips dealt round-robin to the waves
   static int per_cu = 0;
@@ -281,9 +278,7 @@ int stem_launch(StemArgs a, hipStream_t st) {
   const long long want = a.ntiles;
   const long long cap = (long long)per_cu * fvc_num_cus();
   const int grid = (int)(want < cap ? want : cap);
-  hipLaunchKernelGGL((conv_stem_kernel<CINP, NT, K, S, ACT, NW>), dim3(grid), dim3(kThreads), lds, st, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_stem_kernel<CINP, NT, K, S, ACT, NW>, dim3(grid), dim3(kThreads), lds, st, a);
 }
 
 template <int CINP, int NT, int K, int S>
@@ -329,9 +324,7 @@ size_t fvc_conv_stem_wpack_bytes(int cin, int cout, int ksize) {
 int fvc_conv_stem_pack_weight(const float* w, int cin, int cout, int ksize, void* wp, float* osc_out) {
   if (!w || !wp || !osc_out || !fvc_conv_stem_wpack_bytes(cin, cout, ksize)) return FVC_EINVAL;
   const int cinp = stem_cinp(cin), ns = stem_steps(cinp, ksize), nt = cout / 32, kt = ksize * ksize;
-  double mx = 0.0;
-  for (int i = 0; i < cout * cin * kt; ++i) mx = fabs((double)w[i]) > mx ? fabs((double)w[i]) : mx;
-  const int kw = fvc_split_kw(mx);
+  const int kw = fvc_split_kw_of(w, (size_t)cout * cin * kt);
   const float sc = ldexpf(1.f, kw);
   *osc_out = ldexpf(1.f, -kw);
   _Float16* out = (_Float16*)wp;
@@ -381,7 +374,7 @@ int fvc_conv2d_nhwc_stem(const float* x, const void* wpack, float osc, const flo
   if (nt >= (1ll << 31)) return FVC_EINVAL;
   a.ntiles = (int)nt;
   a.osc = osc;
-  a.osc_c = osc * (1.f / 2048.f);
+  a.osc_c = fvc_lo_scale(osc);
   a.ovf = overflow_flag;
   const hipStream_t st = (hipStream_t)stream;
   if (cinp == 8 && ksize == 3 && stride == 1 && cout == 64) return stem_act<8, 2, 3, 1>(a, act, st);

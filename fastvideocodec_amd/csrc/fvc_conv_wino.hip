@@ -941,13 +941,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
 
 template <int IOP, int POST, int RES, int ACT, bool UP = false>
 static int wino_launch4(const WinoArgs& a, int grid, hipStream_t s) {
-  const int lds = UP ? kLdsUp : kLds;
-  const hipError_t e = hipFuncSetAttribute((const void*)conv_wino_kernel<IOP, POST, RES, ACT, UP>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return -(int)e;
-  hipLaunchKernelGGL((conv_wino_kernel<IOP, POST, RES, ACT, UP>), dim3(grid), dim3(256), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_wino_kernel<IOP, POST, RES, ACT, UP>, dim3(grid), dim3(256), UP ? kLdsUp : kLds, s, a);
 }
 
 // the fused upsample-add input form: plain conv (no residual, no pool / tap epilogue)
@@ -1021,11 +1015,11 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   a.chunks_per_col = fvc_cdiv(a.tiles_y, a.chunk);
   a.nchunks = batch * a.ngroups * a.chunks_per_col;
   a.osc = osc;
-  a.osc_c = osc * (1.0f / 2048.f);
+  a.osc_c = fvc_lo_scale(osc);
   a.ovf = ovf;
   a.tw = (const uint4*)tw;
   a.tosc = tosc;
-  a.tosc_c = tosc * (1.0f / 2048.f);
+  a.tosc_c = fvc_lo_scale(tosc);
   a.pcp = pcp;
   a.xp = a.yp = pitch;
   a.xl = xl;
@@ -1114,9 +1108,7 @@ size_t fvc_wino_tap_wpack_bytes(int np) { return np > 0 && np <= 32 ? (size_t)2 
 // v_mfma_f32_16x16x32_f16 A operand), scaled by 2^kt (max |T| 2^kt in [2^13, 2^14))
 int fvc_wino_tap_pack_weight(const float* w, void* wp, float* osc_out, int np) {
   if (!w || !wp || !osc_out || !fvc_wino_tap_wpack_bytes(np)) return FVC_EINVAL;
-  double mx = 0.0;
-  for (int i = 0; i < np * kC; ++i) mx = fabs((double)w[i]) > mx ? fabs((double)w[i]) : mx;
-  const int kt = fvc_split_kw(mx);
+  const int kt = fvc_split_kw_of(w, (size_t)np * kC);
   const float sc = ldexpf(1.f, kt);
   *osc_out = ldexpf(1.f, -kt);
   _Float16* out = (_Float16*)wp;

@@ -525,12 +525,7 @@ static int wr7_rows(int batch, int h, int ngroups, int blocks) {
 
 template <int NT, int MODE, int ACT>
 static int wr7_launch3(const Wr7Args& a, int grid, hipStream_t s) {
-  const hipError_t e = hipFuncSetAttribute((const void*)conv_wr7_kernel<NT, MODE, ACT>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-  if (e != hipSuccess) return -(int)e;
-  hipLaunchKernelGGL((conv_wr7_kernel<NT, MODE, ACT>), dim3(grid), dim3(256), kLds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_wr7_kernel<NT, MODE, ACT>, dim3(grid), dim3(256), kLds, s, a);
 }
 
 template <int NT, int MODE>
@@ -653,7 +648,7 @@ int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float
   if (nch >= (1ll << 30)) return FVC_EINVAL;
   a.nchunks = (int)nch;
   a.osc = osc;
-  a.osc_c = osc * (1.f / 2048.f);
+  a.osc_c = fvc_lo_scale(osc);
   a.ovf = overflow_flag;
   const int grid = ncu < a.nchunks ? ncu : a.nchunks;
   a.sched = fvc_dyn_sched(sched, sched_len, 2);

@@ -703,19 +703,15 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
 }
 
 // ------------------------------------------------------------------ host-side geometry
-struct X3Cfg {
-  int cinp, coutp, ntp, cc, wm, wn, nw, nclass, nchunks, th, sin, sout;
+struct X3Cfg : FvcTaps {
+  int cinp, coutp, ntp, cc, wm, wn, nw, nchunks, th;
   int pt;     // pair-tap form (16 output channels, stride 1): (ky, even kx) pairs, see X3Args::pt
   int dx;     // stride-2 transposed conv on fvc_deconv_x3.hip (all classes per staged tile, one chunk)
-  int ntaps[4], nks[4], oy0[4], ox0[4];
-  int tky[4][kMaxTapsX], tkx[4][kMaxTapsX];
-  int tdy[4][kMaxTapsX], tdx[4][kMaxTapsX];
-  int dymin, dymax, dxmin, dxmax;
+  int nks[4];
   long long wcls[4];
   long long wtotal;  // uint4 (16-B) units
 };
-
-static int x3_floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
+static_assert(kMaxTapsX == kFvcMaxTaps, "X3Args and FvcTaps hold the same tap lists");
 
 // LDS A tile: 2*CC/8 planes (hi octets, then lo octets) of ir*ic 16-B pixel entries. The plane
 // stride is the pixel count rounded up to 4 mod 16 entries (64 B mod 256 B), so the staging
@@ -727,8 +723,7 @@ static size_t x3_tile_bytes(int ir, int ic, int cc) { return (size_t)4 * cc * x3
 // Geometry and tile choice. Returns false for layers the x3 path does not take (cinp % 8 != 0,
 // cout <= 4 -> the VALU small-N kernel, > 128 output channels).
 static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg& c) {
-  if (cin <= 0 || cout <= 0 || (ks != 1 && ks != 3 && ks != 5 && ks != 7) || (stride != 1 && stride != 2))
-    return false;
+  if (cin <= 0 || cout <= 0) return false;
   c.cinp = fvc_rup(cin, 4);
   c.coutp = fvc_rup(cout, 4);
   // cin padded to 4 (cin 2 / 3: mvEncoder conv1, resEncoder conv1) runs as one zero-extended octet:
@@ -744,80 +739,17 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   }
   c.ntp = fvc_cdiv(c.coutp, 32);
   if (c.ntp > 4) return false;
-  const int pad = ks / 2;
   c.pt = (!transposed && stride == 1 && c.coutp == 16 && ks >= 3 && fvc_env_int("FVC_X3_PT", 1)) ? 1 : 0;
-  if (!transposed) {
-    c.nclass = 1;
-    c.sin = stride;
-    c.sout = 1;
-    c.ntaps[0] = 0;
-    for (int ky = 0; ky < ks; ++ky)
-      for (int kx = 0; kx < ks; kx += c.pt ? 2 : 1) {
-        const int t = c.ntaps[0]++;
-        c.tky[0][t] = ky; c.tkx[0][t] = kx;
-        c.tdy[0][t] = ky - pad; c.tdx[0][t] = kx - pad;
-      }
-    c.oy0[0] = c.ox0[0] = 0;
-  } else {
-    c.nclass = stride * stride;
-    c.sin = 1;
-    c.sout = stride;
-    for (int py = 0; py < stride; ++py)
-      for (int px = 0; px < stride; ++px) {
-        const int cl = py * stride + px;
-        c.ntaps[cl] = 0;
-        c.oy0[cl] = py; c.ox0[cl] = px;
-        for (int ky = 0; ky < ks; ++ky) {
-          if (((py + pad - ky) % stride + stride) % stride) continue;
-          for (int kx = 0; kx < ks; ++kx) {
-            if (((px + pad - kx) % stride + stride) % stride) continue;
-            const int t = c.ntaps[cl]++;
-            c.tky[cl][t] = ky; c.tkx[cl][t] = kx;
-            c.tdy[cl][t] = x3_floordiv(py + pad - ky, stride);
-            c.tdx[cl][t] = x3_floordiv(px + pad - kx, stride);
-          }
-        }
-      }
-  }
-  c.dymin = c.dxmin = 1 << 20;
-  c.dymax = c.dxmax = -(1 << 20);
-  for (int cl = 0; cl < c.nclass; ++cl)
-    for (int t = 0; t < c.ntaps[cl]; ++t) {
-      c.dymin = c.tdy[cl][t] < c.dymin ? c.tdy[cl][t] : c.dymin;
-      c.dymax = c.tdy[cl][t] > c.dymax ? c.tdy[cl][t] : c.dymax;
-      c.dxmin = c.tdx[cl][t] < c.dxmin ? c.tdx[cl][t] : c.dxmin;
-      c.dxmax = c.tdx[cl][t] > c.dxmax ? c.tdx[cl][t] : c.dxmax;
-    }
-  // stride-2 transposed convs with 64 / 96 / 128 input and 64 / 128 output channels: the
-  // all-classes kernel (fvc_deconv_x3.hip) when two full-channel tile buffers fit in LDS; its pack
-  // is this pack with one channel chunk. FVC_DX=0 keeps them on this kernel (at pack AND launch).
-  c.dx = 0;
-  if (transposed && stride == 2 && c.nclass == 4 && fvc_env_int("FVC_DX", 1) &&
-      (c.cinp == 64 || c.cinp == 96 || c.cinp == 128) && (c.ntp == 2 || c.ntp == 4)) {
-    int maxt = 0;
-    for (int cl = 0; cl < 4; ++cl) maxt = c.ntaps[cl] > maxt ? c.ntaps[cl] : maxt;
-    // items of R input rows x sw columns: 128 channels 8 x 16 (four 2 x 16-pixel strips), fewer
-    // channels 2 x 32 (4 N-tiles) or 4 x 32 (2 N-tiles): 8 wave-tiles of 2 strips x 2 N-tiles or more
-    const int sw = fvc_dx::strip_width(c.cinp);
-    const int R = sw == 16 ? 8 : (c.ntp == 4 ? 2 : 4);
-    const int ir = R + (c.dymax - c.dymin), ic = sw + (c.dxmax - c.dxmin);
-    if (maxt <= fvc_dx::kMaxTaps && fvc_dx::lds_bytes(c.cinp, fvc_dx::plane_pix(ir, ic)) <= 160 * 1024) {
-      c.dx = 1;
-      c.cc = c.cinp;
-      c.nchunks = 1;
-      c.nw = 8;
-      c.wm = 2;
-      c.wn = 2;
-      c.th = R;
-      long long off = 0;
-      for (int cl = 0; cl < 4; ++cl) {
-        c.nks[cl] = fvc_cdiv(c.ntaps[cl] * (c.cc / 8), 2);
-        c.wcls[cl] = off;
-        off += (long long)c.nks[cl] * c.ntp * kFrag;
-      }
-      c.wtotal = off;
-      return true;
-    }
+  if (!fvc_taps(ks, stride, transposed, c.pt, c)) return false;
+  // the all-classes kernel where it takes the layer; its pack is this pack with one channel chunk
+  c.dx = fvc_dx::config(c, c.cinp, c.ntp, kFrag, c.th, c.nks, c.wcls, c.wtotal) ? 1 : 0;
+  if (c.dx) {
+    c.cc = c.cinp;
+    c.nchunks = 1;
+    c.nw = 8;
+    c.wm = 2;
+    c.wn = 2;
+    return true;
   }
   // channel chunk: the largest of 32 / 16 / 8 dividing cinp (shrunk below if the two LDS tile
   // buffers do not fit); FVC_X3_CC overrides for experiments
@@ -852,21 +784,9 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   return true;
 }
 
-// largest weight magnitude -> the pack's power-of-two scale exponent
-static int x3_kw(const float* w, size_t n) {
-  float mx = 0.f;
-  for (size_t i = 0; i < n; ++i) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
-  return fvc_split_kw(mx);
-}
-
 template <int CC, int WM, int WN, int IOP, int POST, int NWV>
 static int x3_launch(const X3Args& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)conv_x3_kernel<CC, WM, WN, IOP, POST, NWV>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((conv_x3_kernel<CC, WM, WN, IOP, POST, NWV>), grid, dim3(NWV * 64), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_x3_kernel<CC, WM, WN, IOP, POST, NWV>, grid, dim3(NWV * 64), lds, s, a);
 }
 
 // exp after the epilogue is only ever taken with an untransformed input (Synthesis_prior_net
@@ -908,153 +828,6 @@ static int x3_launch_cc(int nwv, int wm, int wn, int iop, int post, const X3Args
   return FVC_EINVAL;
 }
 
-// A stride-2 transposed conv on the all-classes kernel (fvc_deconv_x3.hip): R input rows x 32
-// columns per work item, the item's (class, strip pair, N-tile pair) wave-tiles dealt to the 8 waves
-// so that SIMD partners w and w + 4 together carry an equal share of taps (largest first, to the
-// least-loaded SIMD, then to its less-loaded wave). Tap form: one strip x all 4 N-tiles per wave-tile.
-static int run_dx(const X3Cfg& c, const float* x, const void* wpack, float osc, const float* bias, const float* res,
-                  float* y, int batch, int h, int w, int cout, int in_op, int act, int post_op, int cu_reserve,
-                  int* ovf, int* sched, int sched_len, hipStream_t s, const void* tw, float tosc, int pcp,
-                  unsigned y_bytes, unsigned x_bytes) {
-  const bool tap = tw != nullptr;
-  if (tap && res) return FVC_EINVAL;
-  const int R = c.th;
-  const int sw = fvc_dx::strip_width(c.cinp);
-  const int S = R / (32 / sw);  // strips per item
-  const int wm = tap ? 1 : 2, wn = tap ? c.ntp : 2;
-  fvc_dx::DxArgs d;
-  d.x = x;
-  d.w = (const uint4*)wpack;
-  d.bias = bias;
-  d.res = res;
-  d.y = y;
-  d.post_exp = post_op == FVC_POST_EXP ? 1 : 0;
-  d.B = batch;
-  d.H = h;
-  d.W = w;
-  d.cout = cout;
-  d.coutp = c.coutp;
-  d.ntp = c.ntp;
-  d.R = R;
-  d.sw = sw;
-  d.ir = R + (c.dymax - c.dymin);
-  d.ic = sw + (c.dxmax - c.dxmin);
-  d.ps = fvc_dx::plane_pix(d.ir, d.ic);
-  d.dymin = c.dymin;
-  d.dxmin = c.dxmin;
-  d.inv_ic = 1.0f / (float)d.ic;
-  d.tiles_x = fvc_cdiv(w, sw);
-  d.tiles_y = fvc_cdiv(h, R);
-  const long long nitems = (long long)batch * d.tiles_x * d.tiles_y;
-  if (nitems >= (1LL << 30)) return FVC_EINVAL;
-  d.nitems = (int)nitems;
-  d.osc = osc;
-  d.osc_c = osc * (1.0f / 2048.f);
-  d.act_slope = act == FVC_ACT_RELU ? 0.f : (act == FVC_ACT_LRELU ? 0.1f : 1.f);
-  for (int cl = 0; cl < 4; ++cl) {
-    d.nks[cl] = c.nks[cl];
-    d.oy0[cl] = c.oy0[cl];
-    d.ox0[cl] = c.ox0[cl];
-    d.wcls[cl] = c.wcls[cl];
-    for (int t = 0; t <= fvc_dx::kMaxTaps; ++t)
-      d.toff[cl][t] = t < c.ntaps[cl] ? (c.tdy[cl][t] - c.dymin) * d.ic + (c.tdx[cl][t] - c.dxmin) : 0;
-  }
-  // wave-tiles (class, first strip, first N-tile), cost = the class's taps. Two assignments:
-  // unpaired -- largest first to the least-loaded SIMD, then to its less-loaded wave; paired -- the
-  // wave-tiles of one (class, N-tiles) in pairs of strip groups as one job on SIMD partners w and
-  // w + 4 at the same list position, so the two waves stream the same weight fragments together
-  // (one L2 read feeds both through L1). Paired is taken unless its busiest SIMD carries > 15 % more
-  // taps (FVC_DX_PAIR=0/1 forces either).
-  struct WT {
-    int cl, m0, n0, cost;
-  };
-  WT wt[64];
-  int n = 0;
-  for (int cl = 0; cl < 4; ++cl)
-    for (int n0 = 0; n0 < c.ntp; n0 += wn)
-      for (int m0 = 0; m0 < S; m0 += wm) {
-        if (n >= 64) return FVC_EINVAL;
-        wt[n++] = {cl, m0, n0, c.ntaps[cl]};
-      }
-  auto enc = [](const WT& t) { return t.cl | (t.m0 << 4) | (t.n0 << 8); };
-  auto by_cost = [](WT* v, int k) {  // stable insertion sort, descending
-    for (int i = 1; i < k; ++i)
-      for (int j = i; j > 0 && v[j].cost > v[j - 1].cost; --j) {
-        const WT t = v[j];
-        v[j] = v[j - 1];
-        v[j - 1] = t;
-      }
-  };
-  int up[fvc_dx::kWaves][fvc_dx::kMaxWT], upc[fvc_dx::kWaves] = {0};
-  int pp[fvc_dx::kWaves][fvc_dx::kMaxWT], ppc[fvc_dx::kWaves] = {0};
-  int up_max = 0, pp_max = 1 << 30;
-  {  // unpaired
-    WT v[64];
-    for (int i = 0; i < n; ++i) v[i] = wt[i];
-    by_cost(v, n);
-    int sl[4] = {0, 0, 0, 0}, wl[fvc_dx::kWaves] = {0};
-    for (int i = 0; i < n; ++i) {
-      int sm = 0;
-      for (int q = 1; q < 4; ++q) sm = sl[q] < sl[sm] ? q : sm;
-      int wv = wl[sm + 4] < wl[sm] ? sm + 4 : sm;
-      if (upc[wv] == fvc_dx::kMaxWT) wv = wv == sm ? sm + 4 : sm;
-      if (upc[wv] == fvc_dx::kMaxWT) return FVC_EINVAL;
-      up[wv][upc[wv]++] = enc(v[i]);
-      sl[sm] += v[i].cost;
-      wl[wv] += v[i].cost;
-    }
-    for (int q = 0; q < 4; ++q) up_max = sl[q] > up_max ? sl[q] : up_max;
-  }
-  if ((S / wm) % 2 == 0) {  // paired: jobs = consecutive wave-tile pairs of one (class, N-tiles)
-    WT jobs[32];
-    int nj = 0;
-    for (int i = 0; i + 1 < n; i += 2) jobs[nj++] = wt[i];  // wt[i + 1]: same class / N-tiles, next strips
-    int jidx[32];
-    for (int i = 0; i < nj; ++i) jidx[i] = i;
-    for (int i = 1; i < nj; ++i)
-      for (int j = i; j > 0 && jobs[jidx[j]].cost > jobs[jidx[j - 1]].cost; --j) {
-        const int t = jidx[j];
-        jidx[j] = jidx[j - 1];
-        jidx[j - 1] = t;
-      }
-    int sl[4] = {0, 0, 0, 0};
-    bool ok = true;
-    for (int i = 0; i < nj && ok; ++i) {
-      const int j = jidx[i];
-      int sm = 0;
-      for (int q = 1; q < 4; ++q) sm = sl[q] < sl[sm] ? q : sm;
-      if (ppc[sm] == fvc_dx::kMaxWT) {
-        ok = false;
-        break;
-      }
-      pp[sm][ppc[sm]++] = enc(wt[2 * j]);
-      pp[sm + 4][ppc[sm + 4]++] = enc(wt[2 * j + 1]);
-      sl[sm] += 2 * jobs[j].cost;
-    }
-    if (ok) {
-      pp_max = 0;
-      for (int q = 0; q < 4; ++q) pp_max = sl[q] > pp_max ? sl[q] : pp_max;
-    }
-  }
-  const int pair_env = fvc_env_int("FVC_DX_PAIR", -1);
-  const bool paired = pp_max < (1 << 30) && (pair_env == 1 || (pair_env != 0 && pp_max * 100 <= up_max * 115));
-  for (int wv = 0; wv < fvc_dx::kWaves; ++wv)
-    for (int j = 0; j < fvc_dx::kMaxWT; ++j)
-      d.wt[wv][j] = paired ? (j < ppc[wv] ? pp[wv][j] : -1) : (j < upc[wv] ? up[wv][j] : -1);
-  d.y_bytes = y_bytes;
-  d.x_bytes = x_bytes;
-  d.ovf = ovf;
-  d.tw = (const uint4*)tw;
-  d.tosc = tosc;
-  d.tosc_c = tosc * (1.0f / 2048.f);
-  d.pcp = pcp;
-  const int ncu = fvc_persistent_cus(cu_reserve);
-  const int grid = ncu < d.nitems ? ncu : d.nitems;
-  d.sched = fvc_dyn_sched(sched, sched_len, 2);
-  const size_t lds = fvc_dx::lds_bytes(c.cinp, d.ps);
-  return fvc_dx::launch(d, c.cinp, wm, wn, in_op, tap, grid, lds, s);
-}
-
 // tw != null: fused tap epilogue (y receives P [batch][Ho][Wo][pcp], see kPostTap)
 static int run_x3(const float* x, const void* wpack, float osc, const float* bias, const float* res,
                   float* y, int batch, int h, int w, int cin, int cout, int ks, int stride, int transposed,
@@ -1062,7 +835,7 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
                   hipStream_t s, const void* tw = nullptr, float tosc = 0.f, int pcp = 0, float* pool = nullptr) {
   X3Cfg c;
   if (!x3_cfg(cin, cout, ks, stride, transposed, c)) return FVC_EINVAL;
-  if (!x || !wpack || !bias || !y || batch <= 0 || h <= 0 || w <= 0) return FVC_EINVAL;
+  if (!x || !wpack || !bias || !y || batch <= 0) return FVC_EINVAL;
   if (tw) {
     // every output channel in one wave: N-tiles 1, 2 (2 strips per wave) or 4 (1 strip); the
     // channel chunk (and so the weight pack) stays what x3_cfg chose: fewer strips only shrink LDS
@@ -1085,17 +858,10 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   X3Args a;
   a.x = x; a.w = (const uint4*)wpack; a.bias = bias; a.res = res; a.y = y;
   a.tw = (const uint4*)tw; a.pcp = pcp;
-  a.tosc = tosc; a.tosc_c = tosc * (1.0f / 2048.f);
+  a.tosc = tosc; a.tosc_c = fvc_lo_scale(tosc);
   a.B = batch; a.H = h; a.W = w; a.cinp = c.cinp;
   a.coutp = c.coutp; a.cout = cout;
-  if (!transposed) {
-    if (stride == 2 && ((h & 1) || (w & 1))) return FVC_EINVAL;
-    a.Ho = h / stride; a.Wo = w / stride;
-    a.Hq = a.Ho; a.Wq = a.Wo;
-  } else {
-    a.Ho = h * stride; a.Wo = w * stride;
-    a.Hq = h; a.Wq = w;
-  }
+  if (!fvc_out_dims(h, w, stride, transposed, a.Ho, a.Wo, a.Hq, a.Wq)) return FVC_EINVAL;
   // y and res are addressed through buffer descriptors with 32-bit offsets: split batches whose
   // output tensor reaches 4 GB into launches over sub-batches
   const unsigned long long ybytes = (unsigned long long)batch * a.Ho * a.Wo * ych * 4ull;
@@ -1125,8 +891,8 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   a.x_bytes = (unsigned)xbytes;
   a.ovf = ovf;
   if (c.dx)
-    return run_dx(c, x, wpack, osc, bias, res, y, batch, h, w, cout, in_op, act, post_op, cu_reserve, ovf, sched,
-                  sched_len, s, tw, tosc, pcp, a.y_bytes, a.x_bytes);
+    return fvc_dx::run(c, c.cinp, c.coutp, c.ntp, c.th, c.nks, c.wcls, x, wpack, osc, bias, res, y, batch, h, w, cout,
+                       in_op, act, post_op, cu_reserve, ovf, sched, sched_len, s, tw, tosc, pcp, a.y_bytes, a.x_bytes);
   a.sin = c.sin; a.sout = c.sout; a.nclass = c.nclass; a.nchunks = c.nchunks; a.ntp = c.ntp;
   a.dymin = c.dymin; a.dxmin = c.dxmin;
   const int th = c.th;
@@ -1137,10 +903,10 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   if (c.pt && (tw || pool)) return FVC_EINVAL;
   a.half = c.sin == 2 ? (a.ic + 1) / 2 : 0;
   a.inv_ic = 1.0f / (float)a.ic;
-  a.act_slope = act == FVC_ACT_RELU ? 0.f : (act == FVC_ACT_LRELU ? 0.1f : 1.f);
+  a.act_slope = fvc_act_slope(act);
   a.in_op = in_op; a.act = act; a.post_op = post_op;
   a.osc = osc;
-  a.osc_c = osc * (1.0f / 2048.f);
+  a.osc_c = fvc_lo_scale(osc);
   for (int cl = 0; cl < 4; ++cl) {
     const bool v = cl < c.nclass;
     a.nks[cl] = v ? c.nks[cl] : 0;
@@ -1261,7 +1027,7 @@ int fvc_conv_x3_pack_weight(const float* w, void* wp, float* osc_out, int cin, i
   X3Cfg c;
   if (!x3_cfg(cin, cout, ks, stride, transposed, c) || !w || !wp || !osc_out) return FVC_EINVAL;
   const size_t nw = (size_t)cin * cout * ks * ks;
-  const int kw = x3_kw(w, nw);
+  const int kw = fvc_split_kw_of(w, nw);
   const float sc = ldexpf(1.f, kw);
   *osc_out = ldexpf(1.f, -kw);
   _Float16* out = (_Float16*)wp;
@@ -1313,7 +1079,7 @@ size_t fvc_x3_tap_wpack_bytes(int np, int cin) {
 
 int fvc_x3_tap_pack_weight(const float* w, void* wp, float* osc_out, int np, int cin) {
   if (!w || !wp || !osc_out || !fvc_x3_tap_wpack_bytes(np, cin)) return FVC_EINVAL;
-  const int kw = x3_kw(w, (size_t)np * cin);
+  const int kw = fvc_split_kw_of(w, (size_t)np * cin);
   const float sc = ldexpf(1.f, kw);
   *osc_out = ldexpf(1.f, -kw);
   _Float16* out = (_Float16*)wp;

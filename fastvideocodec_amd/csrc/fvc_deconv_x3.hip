@@ -25,6 +25,39 @@
 
 namespace fvc_dx {
 
+constexpr int kMaxTaps = 9;  // taps per parity class (5x5 stride 2: 9, 6, 6, 4)
+constexpr int kWaves = 8;
+constexpr int kMaxWT = 4;    // wave-tiles per wave per work item
+
+// used in this file only; outside the unnamed namespace because the kernels' symbols carry its name
+struct DxArgs {
+  const float* x;     // [B][H][W][cinp] fp32
+  const uint4* w;     // x3 pack with one channel chunk: [class][k-step][N-tile][hi|lo][lane]
+  const float* bias;
+  const float* res;   // residual [B][2H][2W][coutp] or null (plain epilogue only)
+  float* y;           // [B][2H][2W][coutp], or tap partials [B][2H][2W][pcp]
+  int post_exp;       // exp after the residual (pad channels 0)
+  int B, H, W, cout, coutp, ntp;
+  int R;              // input rows per work item
+  int sw;             // input columns per work item = pixels per strip row (32: 1 x 32 strips, 16: 2 x 16)
+  int ir, ic, ps;     // staged tile rows / columns, LDS plane stride (16-B entries, odd)
+  int dymin, dxmin;
+  float inv_ic;
+  int tiles_x, tiles_y, nitems;
+  float osc, osc_c, act_slope;
+  int nks[4];                    // k-steps per class (taps x cinp / 16)
+  int oy0[4], ox0[4];            // output parity of each class
+  long long wcls[4];             // uint4 offset of each class in the pack
+  int toff[4][kMaxTaps + 1];     // LDS pixel offset of each tap's window, per class
+  int wt[kWaves][kMaxWT];        // wave-tiles per wave: class | first strip << 4 | first N-tile << 8; -1 ends
+  unsigned y_bytes, x_bytes;     // descriptor ranges (< 4 GB, checked by the caller)
+  int* sched;                    // [0] blocks done, [1] next item: zero on entry, reset by the last block
+  int* ovf;
+  const uint4* tw;               // tap epilogue: packed partial weights (fvc_x3_tap_pack_weight)
+  float tosc, tosc_c;
+  int pcp;
+};
+
 namespace {
 
 using namespace fvc_split;
@@ -424,12 +457,7 @@ int launch_t(const DxArgs& a, int grid, size_t lds, hipStream_t s) {
   // fewer channels: 1 x 32-pixel strips
   constexpr int SW = CIN == 128 ? 16 : 32;
   if (a.sw != SW) return FVC_EINVAL;
-  const hipError_t e = hipFuncSetAttribute((const void*)conv_dx_kernel<CIN, WM, WN, IOP, TAP, SW>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return -(int)e;
-  hipLaunchKernelGGL((conv_dx_kernel<CIN, WM, WN, IOP, TAP, SW>), dim3(grid), dim3(kNT), lds, s, a);
-  FVC_CHECK_LAUNCH();
-  return 0;
+  return fvc_launch(conv_dx_kernel<CIN, WM, WN, IOP, TAP, SW>, dim3(grid), dim3(kNT), lds, s, a);
 }
 
 template <int CIN>
@@ -449,12 +477,8 @@ int launch_cin(const DxArgs& a, int wm, int wn, int iop, bool tap, int grid, siz
   return FVC_EINVAL;
 }
 
-}  // namespace
-
-size_t lds_bytes(int cinp, int ps) { return (size_t)kHdr + 2 * (size_t)cinp * 4 * (size_t)ps; }
-
-int plane_pix(int ir, int ic) { return (ir * ic) | 1; }
-
+// cinp in {64, 96, 128}; (wm, wn) = (2, 2) plain epilogue or (1, ntp) with the tap epilogue;
+// iop in {FVC_IN_NONE, FVC_IN_ROUND}
 int launch(const DxArgs& a, int cinp, int wm, int wn, int iop, bool tap, int grid, size_t lds, hipStream_t s) {
   if (grid <= 0 || lds > 160 * 1024) return FVC_EINVAL;
   switch (cinp) {
@@ -465,4 +489,178 @@ int launch(const DxArgs& a, int cinp, int wm, int wn, int iop, bool tap, int gri
   return FVC_EINVAL;
 }
 
+// ------------------------------------------------------------------ host-side planning
+// LDS bytes of one launch (header + two full-channel tile buffers)
+size_t lds_bytes(int cinp, int ps) { return (size_t)kHdr + 2 * (size_t)cinp * 4 * (size_t)ps; }
+// odd plane stride >= ir * ic (conflict-free staging writes of consecutive octets)
+int plane_pix(int ir, int ic) { return (ir * ic) | 1; }
+// strip width of a geometry: 16 (2 x 16-pixel strips, 8-row items) for 128 input channels, else 32
+int strip_width(int cinp) { return cinp == 128 ? 16 : 32; }
+
+// idx = 0 .. n - 1 ordered by cost[stride * idx], largest first, equal costs in index order
+void order_by_cost(const int* cost, int stride, int n, int* idx) {
+  for (int i = 0; i < n; ++i) idx[i] = i;
+  for (int i = 1; i < n; ++i)  // stable insertion sort
+    for (int j = i; j > 0 && cost[stride * idx[j]] > cost[stride * idx[j - 1]]; --j) {
+      const int t = idx[j];
+      idx[j] = idx[j - 1];
+      idx[j - 1] = t;
+    }
+}
+
+// Deals an item's wave-tiles (class, first strip, first N-tile) -- wm strips x wn N-tiles each, S
+// strips and ntp N-tiles per class, cost = the class's taps -- to the 8 waves: wt[wave][], see
+// DxArgs. Two assignments: unpaired -- largest first to the least-loaded SIMD (waves w, w + 4), then
+// to its less-loaded wave; paired -- the wave-tiles of one (class, N-tiles) in pairs of strip groups
+// as one job on SIMD partners w and w + 4 at the same list position, so the two waves stream the
+// same weight fragments together (one L2 read feeds both through L1). Paired is taken unless its
+// busiest SIMD carries > 15 % more taps; pair = 0 / 1 forces either, any other value leaves the
+// choice. false: more wave-tiles than the table holds.
+bool deal(const int ntaps[4], int ntp, int S, int wm, int wn, int pair, int wt[kWaves][kMaxWT]) {
+  int enc[64], cost[64], idx[64];
+  int n = 0;
+  for (int cl = 0; cl < 4; ++cl)
+    for (int n0 = 0; n0 < ntp; n0 += wn)
+      for (int m0 = 0; m0 < S; m0 += wm) {
+        if (n >= 64) return false;
+        enc[n] = cl | (m0 << 4) | (n0 << 8);
+        cost[n++] = ntaps[cl];
+      }
+  int up[kWaves][kMaxWT], upc[kWaves] = {0};
+  int pp[kWaves][kMaxWT], ppc[kWaves] = {0};
+  int up_max = 0, pp_max = 1 << 30;
+  {  // unpaired
+    order_by_cost(cost, 1, n, idx);
+    int sl[4] = {0, 0, 0, 0}, wl[kWaves] = {0};
+    for (int i = 0; i < n; ++i) {
+      int sm = 0;
+      for (int q = 1; q < 4; ++q) sm = sl[q] < sl[sm] ? q : sm;
+      int wv = wl[sm + 4] < wl[sm] ? sm + 4 : sm;
+      if (upc[wv] == kMaxWT) wv = wv == sm ? sm + 4 : sm;
+      if (upc[wv] == kMaxWT) return false;
+      up[wv][upc[wv]++] = enc[idx[i]];
+      sl[sm] += cost[idx[i]];
+      wl[wv] += cost[idx[i]];
+    }
+    for (int q = 0; q < 4; ++q) up_max = sl[q] > up_max ? sl[q] : up_max;
+  }
+  if ((S / wm) % 2 == 0) {  // paired: job j = wave-tiles 2j, 2j + 1 (same class / N-tiles, next strips)
+    const int nj = n / 2;
+    order_by_cost(cost, 2, nj, idx);
+    int sl[4] = {0, 0, 0, 0};
+    bool ok = true;
+    for (int i = 0; i < nj && ok; ++i) {
+      const int j = idx[i];
+      int sm = 0;
+      for (int q = 1; q < 4; ++q) sm = sl[q] < sl[sm] ? q : sm;
+      if (ppc[sm] == kMaxWT) {
+        ok = false;
+        break;
+      }
+      pp[sm][ppc[sm]++] = enc[2 * j];
+      pp[sm + 4][ppc[sm + 4]++] = enc[2 * j + 1];
+      sl[sm] += 2 * cost[2 * j];
+    }
+    if (ok) {
+      pp_max = 0;
+      for (int q = 0; q < 4; ++q) pp_max = sl[q] > pp_max ? sl[q] : pp_max;
+    }
+  }
+  const bool paired = pp_max < (1 << 30) && (pair == 1 || (pair != 0 && pp_max * 100 <= up_max * 115));
+  for (int wv = 0; wv < kWaves; ++wv)
+    for (int j = 0; j < kMaxWT; ++j) wt[wv][j] = paired ? (j < ppc[wv] ? pp[wv][j] : -1) : (j < upc[wv] ? up[wv][j] : -1);
+  return true;
+}
+
+}  // namespace
+
+// Stride-2 transposed convs with 64 / 96 / 128 input and 64 / 128 output channels, when two
+// full-channel tile buffers fit in LDS. FVC_DX=0 keeps them on fvc_conv_x3.hip's kernel (read at
+// pack AND launch: both come through here).
+bool config(const FvcTaps& t, int cinp, int ntp, int frag, int& th, int nks[4], long long wcls[4], long long& wtotal) {
+  if (t.nclass != 4 || t.sout != 2 || !fvc_env_int("FVC_DX", 1) || (cinp != 64 && cinp != 96 && cinp != 128) ||
+      (ntp != 2 && ntp != 4))
+    return false;
+  int maxt = 0;
+  for (int cl = 0; cl < 4; ++cl) maxt = t.ntaps[cl] > maxt ? t.ntaps[cl] : maxt;
+  // items of R input rows x sw columns: 128 channels 8 x 16 (four 2 x 16-pixel strips), fewer
+  // channels 2 x 32 (4 N-tiles) or 4 x 32 (2 N-tiles): 8 wave-tiles of 2 strips x 2 N-tiles or more
+  const int sw = strip_width(cinp);
+  const int R = sw == 16 ? 8 : (ntp == 4 ? 2 : 4);
+  const int ir = R + (t.dymax - t.dymin), ic = sw + (t.dxmax - t.dxmin);
+  if (maxt > kMaxTaps || lds_bytes(cinp, plane_pix(ir, ic)) > 160 * 1024) return false;
+  th = R;
+  wtotal = 0;
+  for (int cl = 0; cl < 4; ++cl) {
+    nks[cl] = fvc_cdiv(t.ntaps[cl] * (cinp / 8), 2);
+    wcls[cl] = wtotal;
+    wtotal += (long long)nks[cl] * ntp * frag;
+  }
+  return true;
+}
+
+// R input rows x 32 columns per work item, the item's wave-tiles dealt to the 8 waves (deal()).
+// Tap form: one strip x all 4 N-tiles per wave-tile.
+int run(const FvcTaps& t, int cinp, int coutp, int ntp, int th, const int nks[4], const long long wcls[4],
+        const float* x, const void* wpack, float osc, const float* bias, const float* res, float* y, int batch, int h,
+        int w, int cout, int in_op, int act, int post_op, int cu_reserve, int* ovf, int* sched, int sched_len,
+        hipStream_t s, const void* tw, float tosc, int pcp, unsigned y_bytes, unsigned x_bytes) {
+  const bool tap = tw != nullptr;
+  if (tap && res) return FVC_EINVAL;
+  const int R = th;
+  const int sw = strip_width(cinp);
+  const int S = R / (32 / sw);  // strips per item
+  const int wm = tap ? 1 : 2, wn = tap ? ntp : 2;
+  DxArgs d;
+  d.x = x;
+  d.w = (const uint4*)wpack;
+  d.bias = bias;
+  d.res = res;
+  d.y = y;
+  d.post_exp = post_op == FVC_POST_EXP ? 1 : 0;
+  d.B = batch;
+  d.H = h;
+  d.W = w;
+  d.cout = cout;
+  d.coutp = coutp;
+  d.ntp = ntp;
+  d.R = R;
+  d.sw = sw;
+  d.ir = R + (t.dymax - t.dymin);
+  d.ic = sw + (t.dxmax - t.dxmin);
+  d.ps = plane_pix(d.ir, d.ic);
+  d.dymin = t.dymin;
+  d.dxmin = t.dxmin;
+  d.inv_ic = 1.0f / (float)d.ic;
+  d.tiles_x = fvc_cdiv(w, sw);
+  d.tiles_y = fvc_cdiv(h, R);
+  const long long nitems = (long long)batch * d.tiles_x * d.tiles_y;
+  if (nitems >= (1LL << 30)) return FVC_EINVAL;
+  d.nitems = (int)nitems;
+  d.osc = osc;
+  d.osc_c = fvc_lo_scale(osc);
+  d.act_slope = fvc_act_slope(act);
+  for (int cl = 0; cl < 4; ++cl) {
+    d.nks[cl] = nks[cl];
+    d.oy0[cl] = t.oy0[cl];
+    d.ox0[cl] = t.ox0[cl];
+    d.wcls[cl] = wcls[cl];
+    for (int i = 0; i <= kMaxTaps; ++i)
+      d.toff[cl][i] = i < t.ntaps[cl] ? (t.tdy[cl][i] - t.dymin) * d.ic + (t.tdx[cl][i] - t.dxmin) : 0;
+  }
+  if (!deal(t.ntaps, ntp, S, wm, wn, fvc_env_int("FVC_DX_PAIR", -1), d.wt)) return FVC_EINVAL;
+  d.y_bytes = y_bytes;
+  d.x_bytes = x_bytes;
+  d.ovf = ovf;
+  d.tw = (const uint4*)tw;
+  d.tosc = tosc;
+  d.tosc_c = fvc_lo_scale(tosc);
+  d.pcp = pcp;
+  const int ncu = fvc_persistent_cus(cu_reserve);
+  const int grid = ncu < d.nitems ? ncu : d.nitems;
+  d.sched = fvc_dyn_sched(sched, sched_len, 2);
+  return launch(d, cinp, wm, wn, in_op, tap, grid, lds_bytes(cinp, d.ps), s);
+}
+
 }  // namespace fvc_dx
+

@@ -1,51 +1,25 @@
 // Internal interface (not exported) between fvc_conv_x3.hip's host dispatcher and the
-// all-classes transposed-conv kernel of fvc_deconv_x3.hip.
+// all-classes transposed-conv kernel of fvc_deconv_x3.hip, which plans its own launches.
 #pragma once
 #include "fvc_common.h"
+#include "fvc_taps.h"
 
 namespace fvc_dx {
 
-constexpr int kMaxTaps = 9;  // taps per parity class (5x5 stride 2: 9, 6, 6, 4)
-constexpr int kWaves = 8;
-constexpr int kMaxWT = 4;    // wave-tiles per wave per work item
+// Does the all-classes kernel take this stride-2 transposed conv (64 / 96 / 128 input channels,
+// ntp = 2 or 4 N-tiles of 32 output channels, FVC_DX not 0)? Then th = input rows per work item and
+// the layout of its weight pack -- the x3 pack with one channel chunk, frag uint4 per (k-step,
+// N-tile): k-steps nks[] and uint4 offset wcls[] of each class, wtotal uint4 in all.
+__attribute__((visibility("hidden"))) bool config(const FvcTaps& t, int cinp, int ntp, int frag, int& th, int nks[4],
+                                                  long long wcls[4], long long& wtotal);
 
-struct DxArgs {
-  const float* x;     // [B][H][W][cinp] fp32
-  const uint4* w;     // x3 pack with one channel chunk: [class][k-step][N-tile][hi|lo][lane]
-  const float* bias;
-  const float* res;   // residual [B][2H][2W][coutp] or null (plain epilogue only)
-  float* y;           // [B][2H][2W][coutp], or tap partials [B][2H][2W][pcp]
-  int post_exp;       // exp after the residual (pad channels 0)
-  int B, H, W, cout, coutp, ntp;
-  int R;              // input rows per work item
-  int sw;             // input columns per work item = pixels per strip row (32: 1 x 32 strips, 16: 2 x 16)
-  int ir, ic, ps;     // staged tile rows / columns, LDS plane stride (16-B entries, odd)
-  int dymin, dxmin;
-  float inv_ic;
-  int tiles_x, tiles_y, nitems;
-  float osc, osc_c, act_slope;
-  int nks[4];                    // k-steps per class (taps x cinp / 16)
-  int oy0[4], ox0[4];            // output parity of each class
-  long long wcls[4];             // uint4 offset of each class in the pack
-  int toff[4][kMaxTaps + 1];     // LDS pixel offset of each tap's window, per class
-  int wt[kWaves][kMaxWT];        // wave-tiles per wave: class | first strip << 4 | first N-tile << 8; -1 ends
-  unsigned y_bytes, x_bytes;     // descriptor ranges (< 4 GB, checked by the caller)
-  int* sched;                    // [0] blocks done, [1] next item: zero on entry, reset by the last block
-  int* ovf;
-  const uint4* tw;               // tap epilogue: packed partial weights (fvc_x3_tap_pack_weight)
-  float tosc, tosc_c;
-  int pcp;
-};
-
-// LDS bytes of one launch (header + two full-channel tile buffers)
-__attribute__((visibility("hidden"))) size_t lds_bytes(int cinp, int ps);
-// odd plane stride >= ir * ic (conflict-free staging writes of consecutive octets)
-__attribute__((visibility("hidden"))) int plane_pix(int ir, int ic);
-// strip width of a geometry: 16 (2 x 16-pixel strips, 8-row items) for 128 input channels, else 32
-inline int strip_width(int cinp) { return cinp == 128 ? 16 : 32; }
-// cinp in {64, 96, 128}; (wm, wn) = (2, 2) plain epilogue or (1, ntp) with the tap epilogue;
-// iop in {FVC_IN_NONE, FVC_IN_ROUND}
-__attribute__((visibility("hidden"))) int launch(const DxArgs& a, int cinp, int wm, int wn, int iop, bool tap,
-                                                 int grid, size_t lds, hipStream_t s);
+// One launch of a layer config() took, th / nks / wcls as it gave them. tw != null: the tap form
+// (y receives the next layer's partials [batch][2h][2w][pcp]; needs ntp = 4 and no residual).
+__attribute__((visibility("hidden"))) int run(const FvcTaps& t, int cinp, int coutp, int ntp, int th, const int nks[4],
+                                              const long long wcls[4], const float* x, const void* wpack, float osc,
+                                              const float* bias, const float* res, float* y, int batch, int h, int w,
+                                              int cout, int in_op, int act, int post_op, int cu_reserve, int* ovf,
+                                              int* sched, int sched_len, hipStream_t s, const void* tw, float tosc,
+                                              int pcp, unsigned y_bytes, unsigned x_bytes);
 
 }  // namespace fvc_dx

@@ -6,6 +6,7 @@
 // CPU path to ~1 ulp.
 #include "fvc_common.h"
 #include "fvc_dist.h"
+#include "fvc_split.h"
 #include <string.h>
 
 #pragma clang fp contract(off)
@@ -1497,7 +1498,7 @@ int fvc_tap_gather_nhwc(const float* P, int pcp, const float* bias, const float*
     return FVC_EINVAL;
   if (transposed ? stride != 2 : stride != 1) return FVC_EINVAL;
   const int Ho = transposed ? h * stride : h, Wo = transposed ? w * stride : w;
-  const float slope = act == FVC_ACT_RELU ? 0.f : (act == FVC_ACT_LRELU ? 0.1f : 1.f);
+  const float slope = fvc_act_slope(act);
   const size_t n = (size_t)batch * Ho * Wo;
   const dim3 g(grid_for(n)), bl(kBlk);
   hipStream_t st = (hipStream_t)s;
@@ -1507,12 +1508,7 @@ int fvc_tap_gather_nhwc(const float* P, int pcp, const float* bias, const float*
     const size_t lds = (size_t)(kGatherTH + 2) * 34 * (pcp + 1) * 4;
 #define FVC_TGL(CO)                                                                                            \
     if (cout == CO) {                                                                                         \
-      if (lds > 64 * 1024)                                                                                    \
-        (void)hipFuncSetAttribute((const void*)k_tap_gather3_lds<CO>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)lds);                                                                  \
-      hipLaunchKernelGGL((k_tap_gather3_lds<CO>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, post_op); \
-      FVC_CHECK_LAUNCH();                                                                                     \
-      return 0;                                                                                               \
+      return fvc_launch(k_tap_gather3_lds<CO>, gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, post_op); \
     }
     FVC_TGL(1) FVC_TGL(2) FVC_TGL(3) FVC_TGL(4)
 #undef FVC_TGL
@@ -1523,13 +1519,8 @@ int fvc_tap_gather_nhwc(const float* P, int pcp, const float* bias, const float*
     const size_t lds = (size_t)(kGatherTH / 2 + 2) * 19 * (pcp + 1) * 4;
 #define FVC_TGT(KS, CO)                                                                                        \
     if (ksize == KS && cout == CO) {                                                                          \
-      if (lds > 64 * 1024)                                                                                    \
-        (void)hipFuncSetAttribute((const void*)k_tap_gather_t2_lds<KS, CO>,                                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-      hipLaunchKernelGGL((k_tap_gather_t2_lds<KS, CO>), gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, \
-                         post_op);                                                                            \
-      FVC_CHECK_LAUNCH();                                                                                     \
-      return 0;                                                                                               \
+      return fvc_launch(k_tap_gather_t2_lds<KS, CO>, gt, dim3(256), lds, st, P, pcp, bias, res, y, h, w, slope, \
+                        post_op);                                                                             \
     }
     FVC_TGT(3, 1) FVC_TGT(3, 2) FVC_TGT(3, 3) FVC_TGT(3, 4)
     FVC_TGT(5, 1) FVC_TGT(5, 2) FVC_TGT(5, 3) FVC_TGT(5, 4)

@@ -179,6 +179,19 @@ static inline int fvc_split_kw(double max_abs) {
   return kw < -100 ? -100 : (kw > 100 ? 100 : kw);
 }
 
+// kw of a contiguous fp32 array (largest |w|; NaNs are skipped)
+static inline int fvc_split_kw_of(const float* w, size_t n) {
+  float mx = 0.f;
+  for (size_t i = 0; i < n; ++i) mx = fabsf(w[i]) > mx ? fabsf(w[i]) : mx;
+  return fvc_split_kw(mx);
+}
+
+// the epilogue's scale of the correction accumulator: the output scale times the lo planes' 2^-11
+static inline float fvc_lo_scale(float osc) { return osc * (1.0f / 2048.f); }
+
+// activation as y = max(t, t * slope): ReLU 0, LeakyReLU 0.1, none 1
+static inline float fvc_act_slope(int act) { return act == FVC_ACT_RELU ? 0.f : (act == FVC_ACT_LRELU ? 0.1f : 1.f); }
+
 // one (already scaled) weight into its place in the hi plane and the lo * 2^11 plane
 static inline void fvc_split_store(_Float16* hi_plane, _Float16* lo_plane, float v) {
   const _Float16 hi = (_Float16)v;

@@ -1,7 +1,8 @@
-"""CPU: every split-precision weight pack entry point of libfvc (host C++) must keep producing the
-bytes and output scales recorded in tests/golden/pack_digests.json. The pack functions share one
-definition of the scale exponent and the hi / lo split (csrc/fvc_split.h); encoder / decoder
-bit-exactness rests on them, and the other pack tests only bound their rounding.
+"""CPU: every weight pack entry point of libfvc (host C++) must keep producing the bytes and
+output scales recorded in tests/golden/pack_digests.json. The split-precision pack functions share
+one definition of the scale exponent and the hi / lo split (csrc/fvc_split.h), and they and the
+f32 pack share one tap geometry (csrc/fvc_taps.h); encoder / decoder bit-exactness rests on them,
+and the other pack tests only bound their rounding.
 
 The weights are filled by integer arithmetic (no RNG stream to drift between numpy versions). The
 golden file holds the SHA-256 of each pack and its scale(s) as float bits. It is regenerated with
@@ -41,6 +42,17 @@ def _run(fn, w, nbytes, args_before=(), args_after=(), nosc=1):
     osc = (ctypes.c_float * nosc)()
     _lib.call(fn, w.ctypes.data, *args_before, wp.ctypes.data, ctypes.addressof(osc), *args_after)
     return wp.tobytes(), list(osc)
+
+
+def _f32(cin, cout, ks, stride, transposed, **kw):
+    """the fp32 pack (fvc_conv_pack_weight): plain floats, no scale"""
+    geo = (cin, cout, ks, stride, transposed)
+    n = _lib.load().fvc_conv_wpack_floats(*geo)
+    assert n > 0
+    w = _weights(cin * cout * ks * ks, **kw)
+    wp = np.zeros(n, np.float32)
+    _lib.call("fvc_conv_pack_weight", w.ctypes.data, wp.ctypes.data, *geo)
+    return wp.tobytes(), []
 
 
 def _x3(cin, cout, ks, stride, transposed, **kw):
@@ -87,6 +99,14 @@ def _stem(cin, cout, k, **kw):
 
 
 CASES = {
+    "f32 8->16 3x3 s1": lambda: _f32(8, 16, 3, 1, 0, seed=18),
+    "f32 128->128 3x3 s1 pipelined": lambda: _f32(128, 128, 3, 1, 0, seed=19),
+    "f32 64->64 3x3 s2": lambda: _f32(64, 64, 3, 2, 0, seed=20),
+    "f32 16->2 7x7 s1 small-N py4": lambda: _f32(16, 2, 7, 1, 0, seed=21),
+    "f32 32->3 3x3 s1 small-N py2": lambda: _f32(32, 3, 3, 1, 0, seed=22),
+    "f32 64->64 5x5 s2 transposed": lambda: _f32(64, 64, 5, 2, 1, seed=23),
+    "f32 16->2 5x5 s2 transposed small-N": lambda: _f32(16, 2, 5, 2, 1, seed=24),
+    "f32 3->64 5x5 s2 cc4": lambda: _f32(3, 64, 5, 2, 0, seed=25),
     "x3 64->64 3x3 s1": lambda: _x3(64, 64, 3, 1, 0, seed=1),
     "x3 8->16 3x3 s1 pair-tap": lambda: _x3(8, 16, 3, 1, 0, seed=2),
     "x3 64->64 5x5 s2 transposed": lambda: _x3(64, 64, 5, 2, 1, seed=3),
