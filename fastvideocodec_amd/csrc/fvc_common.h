@@ -28,6 +28,14 @@ static inline int fvc_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t
 static inline int fvc_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int fvc_rup(int a, int b) { return fvc_cdiv(a, b) * b; }
 
+// blocks for n items at `per` items per block, kept in [1, cap] (the grid-stride and persistent
+// kernels walk the rest)
+static inline unsigned fvc_blocks(size_t n, size_t per, size_t cap) {
+  size_t b = (n + per - 1) / per;
+  if (b > cap) b = cap;
+  return b < 1 ? 1u : (unsigned)b;
+}
+
 // integer value of an environment switch; dflt when unset or empty
 static inline int fvc_env_int(const char* n, int dflt) {
   const char* v = getenv(n);

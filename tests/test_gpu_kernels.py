@@ -97,7 +97,11 @@ def test_conv(dev, case, precision):
         assert float(yc[..., cout:].abs().max()) == 0.0, "pad channels must be zero"
 
 
-@pytest.mark.parametrize("case", [CONV_CASES[i] for i in (9, 12, 19)],
+# a stride-1 5x5 layer: 50 partials per pixel, past the LDS gathers, so the generic k_tap_gather runs
+TAP_GENERIC_CASE = (16, 2, 5, 1, False, 9, 21, K.IN_NONE, K.ACT_NONE, K.POST_EXP, True)
+
+
+@pytest.mark.parametrize("case", [CONV_CASES[i] for i in (9, 12, 19)] + [TAP_GENERIC_CASE],
                          ids=lambda c: f"ci{c[0]}co{c[1]}k{c[2]}s{c[3]}{'T' if c[4] else ''}")
 def test_conv_tap_partial_path(dev, case, monkeypatch):
     """cout <= 4 layers as a 1x1 x3 GEMM to k*k*cout tap partials + fvc_tap_gather_nhwc (forced
@@ -113,6 +117,8 @@ def test_conv_tap_partial_path(dev, case, monkeypatch):
     res = torch.randn(ref.shape, generator=g) if with_res else None
     if res is not None:
         ref = ref + res
+    if post == K.POST_EXP:
+        ref = torch.exp(ref)
     pc = K.PackedConv(w, b, k, s, tr, dev, precision="x3")
     assert pc.tap is not None
     y = pc(to_nhwc(x).to(dev), in_op=in_op, act=act, post=post, res=None if res is None else to_nhwc(res).to(dev))
