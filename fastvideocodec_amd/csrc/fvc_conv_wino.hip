@@ -31,11 +31,11 @@
 // Input: a ring of 8 raw fp32 input rows in LDS filled by LDS-DMA (buffer_load_dwordx4 ... lds, one
 // descriptor per row: padding rows and columns read past it and land as zeros); consecutive items of a block walk down one tile column, so each item
 // stages the 2 new rows of its 4-row window while the previous item computes.
-// LDS input layout (r6): row slot -> 34 columns -> 16 channel quads, the quad index XORed with
+// LDS input layout: row slot -> 34 columns -> 16 channel quads, the quad index XORed with
 // (column >> 1) & 15 (ring_entry): the LDS image of a row is its 34 pixels as they lie in memory, up
 // to that swizzle, so each LDS-DMA instruction reads 4 whole pixels (1 KB contiguous), and the
 // transform's ds_read_b128 of 16 tiles (columns 2t + d) x a quad still covers every bank group
-// once per 16 lanes. (r3-r5: quad-major lines with even / odd column halves; -DFVC_WINO_PIX=0.)
+// once per 16 lanes.
 // Epilogue forms: plain (bias, ReLU / LeakyReLU, residual add), and POOL, which also writes the
 // 2x2 average pool of the output (each pool window is one Winograd tile: ATen's ((x00 + x01) + x10)
 // + x11) / 4, bit-identical to k_avgpool2).
@@ -49,23 +49,16 @@ constexpr int kC = 64;             // input and output channels
 constexpr int kQ = kC / 4;         // channel quads per pixel
 constexpr int kTiles = 16;         // tiles per item: one tile row x 16 tile columns
 constexpr int kCols = 2 * kTiles + 2;  // input columns an item reads
-// staged-row layout. FVC_WINO_PIX 1 (default, r6): pixel-major, entry (local column c, quad Q) at
-// c * 16 + (Q ^ ((c >> 1) & 15)), 34 columns padded to 36 (9 LDS-DMA pieces): every DMA instruction
-// reads 4 whole pixels (1 KB of consecutive bytes). 0 (r3-r5): quad-major, even columns in slots
-// 0..16 and odd ones in 17..33 of a 40-slot line per quad: each DMA instruction gathered 16 B from
-// ~40 pixels. Both give conflict-free ds_read_b128 for the transform's reads (16 tiles x a quad).
-#ifndef FVC_WINO_PIX
-#define FVC_WINO_PIX 1
-#endif
-constexpr bool kPix = FVC_WINO_PIX != 0;
-constexpr int kSlots = 40;         // quad-major form: column slots per (row, quad) line (34 used)
-constexpr int kRowEntries = kPix ? 36 * kQ : kQ * kSlots;   // 16-B entries per staged row (576 / 640)
-constexpr int kRowPieces = kRowEntries / 64;                // LDS-DMA pieces per row (9 / 10)
+// staged-row layout: pixel-major, entry (local column c, quad Q) at c * 16 + (Q ^ ((c >> 1) & 15)),
+// 34 columns padded to 36 (9 LDS-DMA pieces): every DMA instruction reads 4 whole pixels (1 KB of
+// consecutive bytes), and the transform's ds_read_b128 (16 tiles x a quad) is conflict-free.
+constexpr int kRowEntries = 36 * kQ;                       // 16-B entries per staged row (576)
+constexpr int kRowPieces = kRowEntries / 64;               // LDS-DMA pieces per row (9)
 constexpr int kRing = 8;           // staged input rows
-constexpr int kRingBytes = kRing * kRowEntries * 16;  // 73,728 (quad-major: 81,920)
+constexpr int kRingBytes = kRing * kRowEntries * 16;  // 73,728
 constexpr int kZBytes = 4 * 8 * 1024;                 // one Z buffer: 4 waves x 8 planes x 1 KB
 constexpr int kHdr = 512;                             // bias (256 B) + schedule words
-constexpr int kLds = kHdr + kRingBytes + 2 * kZBytes; // 139,776 B (quad-major: 148,480)
+constexpr int kLds = kHdr + kRingBytes + 2 * kZBytes; // 139,776 B
 // fused upsample-add input (UP): the low-resolution rows one item's fix-up reads, [row][pixel][quad]
 // (up to 4 source rows x 20 source columns, the span 4 output rows x 34 output columns of a 2x
 // align_corners=True upsample can reach); Z single-buffered (two barriers per item)
@@ -74,34 +67,8 @@ constexpr int kLowCols = 20;
 constexpr int kLowRowEnt = kLowCols * kQ;                  // 16-B entries per low row (320)
 constexpr int kLowBytes = kLowRows * kLowRowEnt * 16;      // 20,480
 constexpr int kLdsUp = kHdr + kRingBytes + kZBytes + kLowBytes;  // 127,488 B
-// items per schedule chunk (consecutive tile rows of one column): 16 (32 as an experiment switch)
-constexpr int kChunkMin = 16, kChunkMax = 32;
-// knock-outs (experiment builds only; results wrong): FVC_WINO_KO bit 1 = no k-step-1 MFMAs,
-// 2 = no k-step-0 MFMAs (their split VALU kept), 4 = no item barrier, 8 = no finishing pass,
-// 16 = finishing pass without its output stores, 32 = finishing pass without its Z reads,
-// 64 = no staging of the next item's input rows (LDS-DMA issue and its scalar addressing)
-#ifndef FVC_WINO_KO
-#define FVC_WINO_KO 0
-#endif
-// UP knock-outs / forms (experiment builds only): FVC_UP_KO bit 1 = no fix-up body, 2 = no second
-// barrier, 4 = no xu stores, 8 = no LDS write-back, 16 = no low-row DMA; FVC_UP_FORM 1 = per-entry
-// lerp (four low taps per entry) instead of the shared horizontal lerps
-#ifndef FVC_UP_KO
-#define FVC_UP_KO 0
-#endif
-#ifndef FVC_UP_FORM
-#define FVC_UP_FORM 0
-#endif
-#ifndef FVC_UP_FIRST
-#define FVC_UP_FIRST 0
-#endif
-#ifndef FVC_WINO_KO_WAIT
-#define FVC_WINO_KO_WAIT 0
-#endif
-#ifndef FVC_WINO_ALLNOP
-#define FVC_WINO_ALLNOP 0
-#endif
-constexpr bool kAllNop = FVC_WINO_ALLNOP;  // every MFMA block opens with s_nop 1 (diagnostic)
+// items per schedule chunk (consecutive tile rows of one column)
+constexpr int kChunk = 16;
 constexpr int kPostPool = 1;
 constexpr int kPostTap = 2;
 constexpr int kResPost = 1;
@@ -140,8 +107,7 @@ struct WinoArgs {
 
 // 16-B entry of (local column c = 0..33, channel quad Q) within a staged row
 __device__ __forceinline__ int ring_entry(int c, int Q) {
-  if constexpr (kPix) return c * kQ + (Q ^ ((c >> 1) & 15));
-  return Q * kSlots + ((c & 1) ? 17 + (c >> 1) : (c >> 1));
+  return c * kQ + (Q ^ ((c >> 1) & 15));
 }
 
 // UP: quad swizzle of the low rows' LDS image (pixel p's quad q at slot q ^ low_swz(p))
@@ -204,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // = row r of the transform domain
   const int t = lane & 15;    // tile of this lane (MFMA B column / D column)
   const int o = lane >> 4;    // channel octet of this lane within a 32-channel k-step
-  // kPix: byte offset of column 2t in a staged row, and the quad swizzles of columns 2t, 2t + 1
+  // byte offset of column 2t in a staged row, and the quad swizzles of columns 2t, 2t + 1
   // ((2t >> 1) & 15 = t) and 2t + 2, 2t + 3 ((t + 1) & 15), each XORed with the octet's 2 o, x 16 B
   const int pix_b = 2 * t * kQ * 16;
   const int pix_x0 = ((2 * o) ^ t) * 16, pix_x1 = ((2 * o) ^ ((t + 1) & 15)) * 16;
@@ -232,23 +198,17 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
   const int rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
   const float sb = wave == 1 ? 1.f : -1.f;
 
-  // DMA pieces of a staged row this wave issues (piece k of 10 -> wave k & 3) and the lane's
+  // DMA pieces of a staged row this wave issues (piece k of 9 -> wave k & 3) and the lane's
   // part of each: local input column (or a pad slot) and channel-quad offset
   int dma_lc[3], dma_ch[3];
 #pragma unroll
   for (int m = 0; m < 3; ++m) {
     const int e = (wave + 4 * m) * 64 + lane;
-    if constexpr (kPix) {
-      const int c = e >> 4, qq = e & 15;
-      dma_lc[m] = c < 34 ? c : -(1 << 20);
-      dma_ch[m] = 4 * (qq ^ ((c >> 1) & 15));
-    } else {
-      const int c4 = e / kSlots, cs = e - c4 * kSlots;
-      dma_lc[m] = cs < 17 ? 2 * cs : (cs < 34 ? 2 * (cs - 17) + 1 : -(1 << 20));
-      dma_ch[m] = 4 * c4;
-    }
+    const int c = e >> 4, qq = e & 15;
+    dma_lc[m] = c < 34 ? c : -(1 << 20);
+    dma_ch[m] = 4 * (qq ^ ((c >> 1) & 15));
   }
-  const int npiece = wave < kRowPieces - 8 ? 3 : 2;  // 9 / 10 pieces over 4 waves
+  const int npiece = wave < kRowPieces - 8 ? 3 : 2;  // 9 pieces over 4 waves
   // byte offsets of the lane's pieces within an input row of column group g (past the row for
   // padding columns and pad slots: the buffer unit returns zeros)
   auto row_offsets = [&](int g, unsigned (&vo)[3]) {
@@ -335,7 +295,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
   // over; the swizzle is applied on the global side (each lane's 16-B source), so the LDS-DMA image
   // stays lane-linear and every piece still reads 1 KB of consecutive bytes
   auto stage_low = [&](const Fix& f) {
-    if constexpr ((FVC_UP_KO & 16) != 0) return;
     const int e = lane >> 4, qq = lane & 15;  // pixel within the piece, LDS quad slot
 #pragma unroll
     for (int m = 0; m < 5; ++m) {
@@ -346,40 +305,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
         const int px = 4 * pr + e;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rl, (lds_ptr)(low + ((size_t)row * kLowRowEnt + pr * 64) * 16), 16,
                                                  (unsigned)(px * kQ + (qq ^ low_swz(px))) * 16u, 0, 0, 0);
-      }
-    }
-  };
-  auto fixup_entry = [&](const Fix& f) {  // FVC_UP_FORM 1
-    if (f.nlow <= 0) return;
-    for (int cmb = tid; cmb < 4 * 34 * 4; cmb += 256) {
-      const int qlo = cmb & 3, rest = cmb >> 2;
-      const int qhi = rest / 34, sl = rest - 34 * qhi;
-      const int q = 4 * qhi + qlo;
-      const int c = sl < 17 ? 2 * sl : 2 * (sl - 17) + 1;
-      const int ox = 32 * f.g - 1 + c;
-      if ((unsigned)ox >= (unsigned)W) continue;
-      const FvcUpIdx ux = fvc_up_index_scaled(ox, a.wl, a.usx);
-      const int pa = ux.i0 - f.lc0, pb = ux.i1 - f.lc0;
-      const int xa = pa * kQ + (q ^ low_swz(pa)), xb = pb * kQ + (q ^ low_swz(pb));
-      const bool own_c = c >= 1 && c <= 32;
-      for (int ri = 0; ri < f.nr; ++ri) {
-        const int r = f.r0 + ri;
-        if ((unsigned)r >= (unsigned)H) continue;
-        const FvcUpIdx uy = fvc_up_index_scaled(r, a.hl, a.usy);
-        const int ya = (uy.i0 - f.lr0) * kLowRowEnt, yb = (uy.i1 - f.lr0) * kLowRowEnt;
-        float4* const pe =
-            reinterpret_cast<float4*>(ring + ((size_t)((f.sbase + ri) & (kRing - 1)) * kRowEntries + ring_entry(c, q)) * 16);
-        const float4* const lw = reinterpret_cast<const float4*>(low);
-        const float4 sk = *pe;
-        const float4 v = fvc_lerp2d4(lw[ya + xa], lw[ya + xb], lw[yb + xa], lw[yb + xb], uy, ux);
-        const float4 xs = make_float4(sk.x + v.x, sk.y + v.y, sk.z + v.z, sk.w + v.w);
-        if constexpr (!(FVC_UP_KO & 8)) *pe = xs;
-        if constexpr (!(FVC_UP_KO & 4)) {
-          if (own_c && r >= f.own0 && r < f.own1)
-            *reinterpret_cast<float4*>(a.xu + (((size_t)f.b * H + r) * W + ox) * kC + 4 * q) = xs;
-        } else {
-          asm volatile("" ::"v"(xs.x), "v"(xs.y), "v"(xs.z), "v"(xs.w));
-        }
       }
     }
   };
@@ -467,14 +392,10 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
     auto put = [&](int j, int k, const float4& sk, const float4& v) {
       const float4 xs = make_float4(sk.x + v.x, sk.y + v.y, sk.z + v.z, sk.w + v.w);
       if (ok[j] && rv[k]) {
-        if constexpr (!(FVC_UP_KO & 8)) *reinterpret_cast<float4*>((k ? rw1 : rw0) + lo[j]) = xs;
-        if constexpr (!(FVC_UP_KO & 4)) {
-          if (own[j] && ro[k])
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, xs), rxu,
-                                                   (unsigned)(f.r0 + ri0 + k - rxf) * (unsigned)W * kC * 4u + xo[j], 0, 0);
-        } else {
-          asm volatile("" ::"v"(xs.x), "v"(xs.y), "v"(xs.z), "v"(xs.w));
-        }
+        *reinterpret_cast<float4*>((k ? rw1 : rw0) + lo[j]) = xs;
+        if (own[j] && ro[k])
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, xs), rxu,
+                                                 (unsigned)(f.r0 + ri0 + k - rxf) * (unsigned)W * kC * 4u + xo[j], 0, 0);
       }
     };
     auto hlerp = [&](const float4& ta, const float4& tb, const FvcUpIdx& u) {  // fvc_lerp2d's inner steps
@@ -522,12 +443,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
     }
   };
   auto fixup = [&](const Fix& f) {
-    if constexpr ((FVC_UP_KO & 1) != 0) return;
     if (f.nlow <= 0) return;
-    if constexpr (FVC_UP_FORM == 1) {
-      fixup_entry(f);
-      return;
-    }
     if (f.g != fcols_g) {  // wave-uniform: a new column group (at most once per chunk)
       fcols = fix_cols(f.g, f.lc0);
       fcols_g = f.g;
@@ -610,7 +526,6 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
       // the next item's new input rows (2, or 4 after a chunk change), issued between the MFMA
       // blocks of the k-loop (k-th pair of rows at point k) where their issue cost overlaps them
       auto stage_next = [&](int k) {
-        if constexpr (FVC_WINO_KO & 64) return;  // knock-out: no staging of the next item's rows
         if (!nvalid) return;
         if (k == 0 && cont) return;
         const int i0 = 2 * k;
@@ -652,23 +567,16 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
       // software-pipelined: the next k-step's LDS reads and transform sit between this k-step's
       // MFMA blocks (source order is issue order around the asm blocks)
       auto read_raw = [&](int kk, int hh, float4 (&da)[4], float4 (&db)[4]) {
-        (void)pix_b;
-        // patch columns 0..3 of tile t: slots t, 17 + t, t + 1, 18 + t (even / odd column halves)
+        // patch columns d = 0..3 of tile t, quad Q: ring_entry(2t + d, Q) * 16 = (8 kk + hh) ^
+        // (2 o ^ swizzle), per-lane parts hoisted. (Q itself is not read, but the line stays: without
+        // it the lambda no longer captures o, which moves every instantiation's register allocation.)
         const int Q = 8 * kk + 2 * o + hh;
         int e[4];
-        if constexpr (kPix) {  // = ring_entry(2t + d, Q) * 16: (8 kk + hh) ^ (2 o ^ swizzle), per-lane parts hoisted
-          const int cq = (8 * kk + hh) * 16;
-          e[0] = pix_b + (cq ^ pix_x0);
-          e[1] = e[0] + 256;
-          e[2] = pix_b + 512 + (cq ^ pix_x1);
-          e[3] = e[2] + 256;
-        } else {
-          const int e0 = (Q * kSlots + t) * 16;
-          e[0] = e0;
-          e[1] = e0 + 17 * 16;
-          e[2] = e0 + 16;
-          e[3] = e0 + 18 * 16;
-        }
+        const int cq = (8 * kk + hh) * 16;
+        e[0] = pix_b + (cq ^ pix_x0);
+        e[1] = e[0] + 256;
+        e[2] = pix_b + 512 + (cq ^ pix_x1);
+        e[3] = e[2] + 256;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
           da[d] = *reinterpret_cast<const float4*>(rowa + e[d]);
@@ -716,7 +624,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
       auto mfma_q1 = [&](int q, const h8 (&vh)[4], const h8 (&vl)[4]) {  // k-step 1 of position q
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-          if (n == 0 || kAllNop) mfma3<false, true>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
+          if (n == 0) mfma3<false, true>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
           else mfma3<false, false>(acc[q][n], cor[q][n], u[q][n][1][0], u[q][n][1][1], vh[q], vl[q]);
         }
       };
@@ -740,14 +648,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
       for (int q = 0; q < 4; ++q) {
 #pragma unroll
         for (int n = 0; n < 4; ++n)
-          if constexpr (FVC_WINO_KO & 2) {
-            split2(v1[n][2 * q], v1[n][2 * q + 1], hw1[n][q], lw1[n][q]);
-            acc[q][n] = cor[q][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-            asm volatile("" : "+v"(acc[q][n]) : "v"(vh0[q]), "v"(vl0[q]));
-          } else {
-          ((q == 0 && n == 0) || kAllNop ? wino_mfma3_split<true> : wino_mfma3_split<false>)(acc[q][n], cor[q][n], u[q][n][0][0], u[q][n][0][1], vh0[q], vl0[q], v1[n][2 * q],
+          (q == 0 && n == 0 ? wino_mfma3_split<true> : wino_mfma3_split<false>)(acc[q][n], cor[q][n], u[q][n][0][0], u[q][n][0][1], vh0[q], vl0[q], v1[n][2 * q],
                            v1[n][2 * q + 1], hw1[n][q], lw1[n][q]);
-          }
         if (q == 1) stage_next(1);
       }
 #pragma unroll
@@ -756,13 +658,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
         vl1[q] = __builtin_bit_cast(h8, v4u{lw1[q][0], lw1[q][1], lw1[q][2], lw1[q][3]});
       }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if constexpr (FVC_WINO_KO & 1) {
-          asm volatile("" : "+v"(acc[q][0]), "+v"(cor[q][0]) : "v"(vh1[q]), "v"(vl1[q]));
-        } else {
-          mfma_q1(q, vh1, vl1);
-        }
-      }
+      for (int q = 0; q < 4; ++q) mfma_q1(q, vh1, vl1);
       wino_mfma_drain(acc, cor);
 
       // ---- column combination Z[r][j] = sum_q M[r][q] A[q][j] (M in units of 2^kw: the scale is
@@ -788,28 +684,17 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
         *reinterpret_cast<f32x4*>(zw + ((wave * 2 + 0) * 4 + n) * 1024 + lane * 16) = z0;
         *reinterpret_cast<f32x4*>(zw + ((wave * 2 + 1) * 4 + n) * 1024 + lane * 16) = z1;
       }
-#if FVC_WINO_KO_WAIT
-      asm volatile("" ::: "memory");  // knock-out (experiment builds only): no wait for the next item's rows
-#else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces of the next item
-#endif
-      if constexpr (!(FVC_WINO_KO & 4)) __syncthreads();
+      __syncthreads();
       if (first) nnp = decode(sq[2 + (ntaken & 1)]);  // published by this item's barrier
-      if constexpr (UP && FVC_UP_FIRST) fixup(nf);  // experiment: the fix-up before the finishing pass
 
       // ---- finishing pass: wave w -> output channels 16w..16w+15 of the item's 16 tiles
-      if constexpr (!(FVC_WINO_KO & 8)) {
       f32x4 z[4][2];
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          if constexpr (FVC_WINO_KO & 32) {
-            z[p][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            asm volatile("" : "+v"(z[p][j]));
-          } else {
-            z[p][j] = *reinterpret_cast<const f32x4*>(zw + ((p * 2 + j) * 4 + wave) * 1024 + lane * 16);
-          }
+          z[p][j] = *reinterpret_cast<const f32x4*>(zw + ((p * 2 + j) * 4 + wave) * 1024 + lane * 16);
       const f32x4 bj = *reinterpret_cast<const f32x4*>(sbias + cbase);
       f32x4 yv[2][2];
 #pragma unroll
@@ -834,10 +719,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
             vv[2 * cp + 1] = tv.y;
           }
           yv[i][j] = vv;
-          if constexpr (POST != kPostTap) {
-            if constexpr (FVC_WINO_KO & 16) asm volatile("" ::"v"(vv));
-            else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, vv), ry, yo[i][j], 0, FVC_STORE_AUX);
-          }
+          if constexpr (POST != kPostTap)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, vv), ry, yo[i][j], 0, 0);
         }
       if constexpr (POST == kPostPool) {
         f32x4 pv;
@@ -902,11 +785,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const WinoArgs a) {
         }
       }
 
-      }  // FVC_WINO_KO & 8
-
       if constexpr (UP) {  // the next item's new rows: S -> X in place (and to xu), then published
-        if constexpr (!FVC_UP_FIRST) fixup(nf);
-        if constexpr (!(FVC_UP_KO & 2)) __syncthreads();
+        fixup(nf);
+        __syncthreads();
       }
 
       // ---- advance
@@ -1008,10 +889,9 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   a.tiles_y = (h + 1) / 2;
   a.ngroups = fvc_cdiv(w, 32);
   // 16 tile rows per chunk. Longer chunks re-stage fewer halo rows (a chunk's first item stages 4
-  // rows, later ones 2): FVC_WINO_CHUNK=32 (experiments) measured equal on the 1088x1920 and
-  // 544x960 layers and 4-5 % slower on the 272x480 quarters (profiles/r6/wino_ko/chunk.txt).
-  // The result does not depend on it.
-  a.chunk = fvc_env_int("FVC_WINO_CHUNK", kChunkMin) == kChunkMax ? kChunkMax : kChunkMin;
+  // rows, later ones 2) but 32 measured equal on the 1088x1920 and 544x960 layers and 4-5 % slower
+  // on the 272x480 quarters (profiles/r6/wino_ko/chunk.txt). The result does not depend on it.
+  a.chunk = kChunk;
   a.chunks_per_col = fvc_cdiv(a.tiles_y, a.chunk);
   a.nchunks = batch * a.ngroups * a.chunks_per_col;
   a.osc = osc;

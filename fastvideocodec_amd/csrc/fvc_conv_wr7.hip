@@ -46,28 +46,6 @@ namespace {
 
 using namespace fvc_split;
 
-// experiment knobs (compile-time; the product build uses the defaults): the gap after which quad
-// 1's raw columns are read, and whether waves 0..2 use the 3 + 3-term transform (branch) or every
-// wave the general 4 + 4-term one (branch-free)
-#ifndef FVC_WR7_Q1GAP
-#define FVC_WR7_Q1GAP 4
-#endif
-#ifndef FVC_WR7_SPEC
-#define FVC_WR7_SPEC 0
-#endif
-#ifndef FVC_WR7_DIST
-#define FVC_WR7_DIST 2
-#endif
-// knock-outs (experiment builds only; results wrong): bit 0 no transform (raw reads + VALU),
-// bit 1 no finishing (partial reads, stores), bit 2 no per-step barrier, bit 3 no MFMAs, bit 4 no
-// partial-output writes (combine + ds_write)
-#ifndef FVC_WR7_KO
-#define FVC_WR7_KO 0
-#endif
-#ifndef FVC_WR7_SPREAD
-#define FVC_WR7_SPREAD 0
-#endif
-
 constexpr int kCi = 32;                         // input channels per launch
 constexpr int kQ = kCi / 4;                     // channel quads
 constexpr int kSlots = 40;                      // column slots per (row, quad) line: 19 even + 19 odd used
@@ -79,7 +57,8 @@ constexpr int kHdr = 256;                               // bias (128 B) + work-i
 constexpr int kResBytes = 4 * 3 * 64 * 16;             // residual rows (mode 2): [wave][3 slots][lane] f32x4
 constexpr int kLds = kHdr + kRawBytes + 2 * kZBytes + 1024 + kResBytes;  // 128,256 (+ the dummy-DMA sink)
 constexpr int kRowsMax = 128;                   // output rows per work item, at most (wr7_rows)
-constexpr int kDist = FVC_WR7_DIST;             // raw rows are staged kDist steps before their transform
+constexpr int kDist = 2;                       // raw rows are staged kDist steps before their transform
+constexpr int kQ1Gap = 4;                      // MFMA block after which quad 1's raw columns are read
 constexpr int kModeFull = 0;     // y = act(conv + bias)
 constexpr int kModePartial = 1;  // y = conv (first input-channel half)
 constexpr int kModeAdd = 2;      // y = act(conv + bias + y) (second input-channel half)
@@ -221,29 +200,16 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
       (hq ? T.x1 : T.x0)[l] = *reinterpret_cast<const float4*>(line + slot * 16);
     }
   };
-  // waves 0..2: V_a, V_b = e +- o over 3 + 3 columns (E0 = O3 = 0); wave 3: V0 = e, V7 = o over
-  // 4 + 4 columns (a wave-uniform branch: 8 VALU per channel either way)
+  // every wave the general 4 + 4-term form, branch-free (E0 = O3 = 0 on waves 0..2): waves 0..2
+  // V_a, V_b = e +- o, wave 3 V0 = e, V7 = o
   auto tx_chan = [&](Tx& T, int hq, int c) {
     const float4* const x = hq ? T.x1 : T.x0;
     auto ch = [&](const float4& v) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); };
-    // (the empty asm keeps hipcc from if-converting the uniform branch into both paths + selects)
-    if (!FVC_WR7_SPEC) {
-      const float e = fmaf(E3, ch(x[6]), fmaf(E2, ch(x[4]), fmaf(E1, ch(x[2]), E0 * ch(x[0]))));
-      const float od = fmaf(O3, ch(x[7]), fmaf(O2, ch(x[5]), fmaf(O1, ch(x[3]), O0 * ch(x[1]))));
-      const bool w3 = wave == 3;
-      T.va[4 * hq + c] = w3 ? e : e + od;
-      T.vb[4 * hq + c] = w3 ? od : e - od;
-    } else if (wave != 3) {
-      asm volatile("");
-      const float e = fmaf(E3, ch(x[6]), fmaf(E2, ch(x[4]), E1 * ch(x[2])));
-      const float od = fmaf(O2, ch(x[5]), fmaf(O1, ch(x[3]), O0 * ch(x[1])));
-      T.va[4 * hq + c] = e + od;
-      T.vb[4 * hq + c] = e - od;
-    } else {
-      asm volatile("");
-      T.va[4 * hq + c] = fmaf(E3, ch(x[6]), fmaf(E2, ch(x[4]), fmaf(E1, ch(x[2]), E0 * ch(x[0]))));
-      T.vb[4 * hq + c] = fmaf(O3, ch(x[7]), fmaf(O2, ch(x[5]), fmaf(O1, ch(x[3]), O0 * ch(x[1]))));
-    }
+    const float e = fmaf(E3, ch(x[6]), fmaf(E2, ch(x[4]), fmaf(E1, ch(x[2]), E0 * ch(x[0]))));
+    const float od = fmaf(O3, ch(x[7]), fmaf(O2, ch(x[5]), fmaf(O1, ch(x[3]), O0 * ch(x[1]))));
+    const bool w3 = wave == 3;
+    T.va[4 * hq + c] = w3 ? e : e + od;
+    T.vb[4 * hq + c] = w3 ? od : e - od;
   };
   auto tx_split = [&](Tx& T, int i) {  // i < 4: V_a pair i, else V_b pair i - 4
     if (i < 4) split2(T.va[2 * i], T.va[2 * i + 1], T.hwa[i], T.lwa[i]);
@@ -388,21 +354,16 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
       auto gap = [&](int k) {
         // LDS reads two blocks ahead of their first use; quad 1's columns are read once quad 0's
         // are consumed (the two sets never live together: VGPR budget)
-        if ((FVC_WR7_KO & 1) && k != 3 && k != 0) return;
-        if ((FVC_WR7_KO & 2) && k == 3) return;
         if (k == 0) {
-          if (!(FVC_WR7_KO & 1)) tx_read(T, rrow, 0);
-          if (!(FVC_WR7_KO & 2)) finish_read(zb ^ 1, y - 1, P, bj, rv);
+          tx_read(T, rrow, 0);
+          finish_read(zb ^ 1, y - 1, P, bj, rv);
         } else if (k == 2) tx_chan(T, 0, 0);
         else if (k == 3) finish_row(yimg, y - 1, so, prev, P, bj, rv);
         else if (k >= 4 && k <= 6) tx_chan(T, 0, k - 3);
-        else if (!FVC_WR7_SPREAD && k >= 8 && k <= 11) tx_chan(T, 1, k - 8);
-        else if (FVC_WR7_SPREAD && k >= 8 && k <= 14 && !(k & 1)) tx_chan(T, 1, (k - 8) >> 1);
-        else if (!FVC_WR7_SPREAD && k >= 12 && k <= 19) tx_split(T, k - 12);
-        else if (FVC_WR7_SPREAD && k >= 15 && k <= 26 && k != 17 && k != 20 && k != 23 && k != 26)
-          tx_split(T, k - 15 - (k > 17) - (k > 20) - (k > 23));
-        else if (k == (FVC_WR7_SPREAD ? 27 : 20)) tx_store(T, ic<(S + 7) & 7>{});
-        if (k == FVC_WR7_Q1GAP) tx_read(T, rrow, 1);
+        else if (k >= 8 && k <= 11) tx_chan(T, 1, k - 8);
+        else if (k >= 12 && k <= 19) tx_split(T, k - 12);
+        else if (k == 20) tx_store(T, ic<(S + 7) & 7>{});
+        if (k == kQ1Gap) tx_read(T, rrow, 1);
       };
       auto row_mfmas = [&](auto DY_c) {
         constexpr int DY = decltype(DY_c)::value;
@@ -411,10 +372,7 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
         for (int pp = 0; pp < 2; ++pp)
 #pragma unroll
           for (int n = 0; n < NT; ++n) {
-            if (FVC_WR7_KO & 8) {
-              if (DY == 0) acc[pp][n] = cor[pp][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-              asm volatile("" : "+v"(acc[pp][n]), "+v"(cor[pp][n]) : "v"(vh[VS][pp]), "v"(vl[VS][pp]));
-            } else if (DY == 0 && pp == 0 && n == 0)
+            if (DY == 0 && pp == 0 && n == 0)
               mfma3<true, true>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp], vl[VS][pp]);
             else
               mfma3<DY == 0, false>(acc[pp][n], cor[pp][n], u[pp][DY][n][0], u[pp][DY][n][1], vh[VS][pp],
@@ -443,10 +401,6 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
       char* const zw = zbuf + zb * kZBytes;
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
-        if (FVC_WR7_KO & 16) {
-          asm volatile("" :: "v"(acc[0][n]), "v"(acc[1][n]), "v"(cor[0][n]), "v"(cor[1][n]));
-          continue;
-        }
         f32x4 ma, mb;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -466,10 +420,9 @@ __global__ __launch_bounds__(256, 1) void conv_wr7_kernel(const Wr7Args a) {
       // and (mode 2) row y's partial sum, staged one step ago just before it: every wave issues per
       // step [1 residual DMA,] 2 raw-row DMA operations and 1 store, so the ones younger than that
       // row's DMA are the previous step's store and this step's 3 (4)
-      if constexpr (kDist == 3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-      else if constexpr (MODE == kModeAdd) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      if constexpr (MODE == kModeAdd) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      if (!(FVC_WR7_KO & 4)) __syncthreads();
+      __syncthreads();
       zb ^= 1;
       ++y;
     };

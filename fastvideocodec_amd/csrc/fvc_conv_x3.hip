@@ -46,33 +46,7 @@ using namespace fvc_split;
 
 constexpr int kMaxTapsX = 49;
 
-// FVC_X3_KO (compile-time, experiment builds only -- wrong results): knock out parts of the k-loop to
-// find the binding unit. bit 0: no weight loads (registers), bit 1: no staging of later chunks,
-// bit 2: no LDS operand reads (registers), bit 3: no MFMAs, bit 4: weights always from k-step 0
-// (L1-resident), bit 5: staging always from tile 0 / chunk 0 (cache-resident).
-#ifndef FVC_X3_KO
-#define FVC_X3_KO 0
-#endif
-constexpr int kKO = FVC_X3_KO;
-// FVC_X3_SCHED (compile-time, experiments): how each half-step's instruction stream is ordered.
-// 0: sched_barrier pins [next operands' loads] then [MFMAs]; 1: compiler's own order within a
-// half-step; 2: sched_group_barrier interleave, one load between consecutive MFMAs
-// (profiles/r2/x3_experiments: 1 and 2 within +-5 % per geometry, 1 -1 % in the pipelined bench)
-#ifndef FVC_X3_SCHED
-#define FVC_X3_SCHED 0
-#endif
-constexpr int kSched = FVC_X3_SCHED;
-// FVC_X3_ACC1 (compile-time variant): one accumulator. The weight pack carries three planes, hi,
-// (w - hi) and hi * 2^-11 (the last two may be fp16 subnormals: their absolute error 2^-25 is
-// 2^-39 of the layer's largest weight, which the pack scales into [2^13, 2^14)), so
-//     acc += hi_w * hi_x + (w - hi)_w * hi_x + (hi_w 2^-11) * (lo_x 2^11)
-// sums the same three products in one fp32 accumulator: half the accumulator registers and one
-// FMA per output in the epilogue, for 1.5x the weight operand bytes.
-#ifndef FVC_X3_ACC1
-#define FVC_X3_ACC1 0
-#endif
-constexpr int kAcc1 = FVC_X3_ACC1;
-constexpr int kNPL = kAcc1 ? 3 : 2;        // weight planes per (k-step, N-tile): hi, lo [, hi 2^-11]
+constexpr int kNPL = 2;                   // weight planes per (k-step, N-tile): hi, lo
 constexpr int kFrag = 64 * kNPL;          // uint4 per (k-step, N-tile)
 // internal post-op of the fused tap path (fvc_conv2d_nhwc_x3_tap): not part of the public enum
 constexpr int kPostTap = 2;
@@ -123,28 +97,6 @@ struct X3Args {
   int pt;
 };
 
-// FVC_X3_TRACE (compile-time, diagnostic builds only): per wave, s_memtime sums of the k-loop's
-// segments (0 prologue, 1 operand/staging load issue, 2 MFMA blocks, 3 staging split + LDS write,
-// 4 chunk end: leftover staging + barrier, 5 epilogue, 6 whole wave) into g_x3_trace. Each stamp
-// drains lgkmcnt, so read shares, not lengths.
-#ifndef FVC_X3_TRACE
-#define FVC_X3_TRACE 0
-#endif
-constexpr int kTraceVals = 8;
-constexpr int kTraceSlots = 1 << 16;
-#if FVC_X3_TRACE
-__device__ unsigned long long g_x3_trace[kTraceSlots * kTraceVals];
-#endif
-__device__ __forceinline__ unsigned long long x3_stamp() {
-  unsigned long long t = 0;
-#if FVC_X3_TRACE
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-  return t;
-}
-
 // Wave grid: the NWV waves of a block stack vertically, each WM strips x WN N-tiles; every wave owns
 // the block's N-tiles nt0 .. nt0 + WN - 1 and fetches their weight fragments itself from L2.
 template <int CC, int WM, int WN, int IOP, int POST, int NWV>
@@ -166,16 +118,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
   _Float16* const sdump = smh + 256;  // 32 B sink for staging writes of items past the tile
   int* const squeue = reinterpret_cast<int*>(smh) + 144;  // item k of this block at squeue[k & 3]
 
-  unsigned long long tr[kTraceVals] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long tr_t0 = x3_stamp();
-  const unsigned long long tr_begin = tr_t0;
-  auto TR = [&](int i) {  // close the running segment, attributing it to i
-    if constexpr (FVC_X3_TRACE != 0) {
-      const unsigned long long t1 = x3_stamp();
-      tr[i] += t1 - tr_t0;
-      tr_t0 = t1;
-    }
-  };
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform (scalar branches)
@@ -253,14 +195,12 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     bool ok;
   };
   auto fetch = [&](int e, int tile, int ch, Stage& st) {
-    if constexpr ((kKO & 2) != 0) return;
     st.ok = e < tile_items;  // past the end: loads of a clamped index, no LDS write
     e = st.ok ? e : tile_items - 1;
     const int o = e & (C8 - 1);
     const int p = e / C8;
     const int r = (int)(((float)p + 0.5f) * a.inv_ic);  // exact: p < 2^14, ic <= 128
     const int c = p - r * a.ic;
-    if constexpr ((kKO & 32) != 0) { tile = 0; ch = 0; }
     const int iy = (tile / tiles_x) * TH * a.sin + a.dymin + r;
     const int ix = (tile % tiles_x) * TWo * a.sin + a.dxmin + c;
     const bool inb = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
@@ -273,7 +213,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
     st.dst = o * a.ps + (r * a.ic + cpos) * 8;  // plane o (hi), pixel-minor
   };
   auto store = [&](_Float16* t, const Stage& st) {
-    if constexpr ((kKO & 2) != 0) return;
     float v[8] = {st.v0.x, st.v0.y, st.v0.z, st.v0.w, st.v1.x, st.v1.y, st.v1.z, st.v1.w};
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = in_op_t<IOP>(v[i]);  // zero padding stays zero
@@ -310,15 +249,12 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
   // without a memory wait inside the k-loop
   int tap_tab = a.toff[cls][lane <= kMaxTapsX ? lane : kMaxTapsX];
   __syncthreads();
-  TR(0);
 
   struct Ops {
     h8 ah[WM], al[WM];
-    uint4 bh[WN], bl[WN], bm[kAcc1 ? WN : 1];
+    uint4 bh[WN], bl[WN];
   };
-  f32x16 acc[WM][WN], cor[kAcc1 ? 1 : WM][kAcc1 ? 1 : WN];
-  uint4 ko_w = a.w[lane];
-  h8 ko_a = *reinterpret_cast<const h8*>(tile0 + 8 * lane);
+  f32x16 acc[WM][WN], cor[WM][WN];
   int buf = 0;  // LDS buffer holding the chunk being multiplied
   const __amdgpu_buffer_rsrc_t ry =
       __builtin_amdgcn_make_buffer_rsrc((void*)a.y, (short)0, (int)a.y_bytes, kRsrcFlags);
@@ -343,7 +279,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           acc[m][n][r] = 0.f;
-          if constexpr (!kAcc1) cor[m][n][r] = 0.f;
+          cor[m][n][r] = 0.f;
         }
 
     // K loop over channel chunks. Two operand register sets (ping-pong, no copies). Each
@@ -373,77 +309,39 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         }
 #pragma unroll
         for (int m = 0; m < WM; ++m) {
-          if constexpr ((kKO & 4) != 0) {
-            op.ah[m] = ko_a + (_Float16)(q + m);
-            op.al[m] = ko_a;
-            continue;
-          }
           op.ah[m] = *reinterpret_cast<const h8*>(cur + pix0 + m * pix_m + toff);
           op.al[m] = *reinterpret_cast<const h8*>(cur + pix0 + m * pix_m + toff + C8 * a.ps);
         }
-        const uint4* wk = ((kKO & 16) ? wcls : wch) + ((size_t)((kKO & 16) ? 0 : q) * a.ntp + ntw) * kFrag + lane;
+        const uint4* wk = wch + ((size_t)q * a.ntp + ntw) * kFrag + lane;
 #pragma unroll
         for (int n = 0; n < WN; ++n) {
-          if constexpr ((kKO & 1) != 0) {
-            op.bh[n] = ko_w + (unsigned)(q + n);
-            op.bl[n] = ko_w;
-            continue;
-          }
           op.bh[n] = wk[n * kFrag];
           op.bl[n] = wk[n * kFrag + 64];
-          if constexpr (kAcc1) op.bm[n] = wk[n * kFrag + 128];
         }
       };
       // weights as the A (row) operand, pixels as B: the 32x32 result is channel x pixel, so
       // each lane ends up with 4 consecutive channels of one pixel per register group (16-B
       // epilogue stores)
       auto mfmas = [&](const Ops& op) {
-        if constexpr ((kKO & 8) != 0) {
-#pragma unroll
-          for (int m = 0; m < WM; ++m)
-#pragma unroll
-            for (int n = 0; n < WN; ++n) acc[m][n][0] += (float)op.ah[m][0] + (float)__builtin_bit_cast(h8, op.bh[n])[0];
-          return;
-        }
 #pragma unroll
         for (int m = 0; m < WM; ++m)
 #pragma unroll
           for (int n = 0; n < WN; ++n) {
             const h8 wh = __builtin_bit_cast(h8, op.bh[n]);
             const h8 wl = __builtin_bit_cast(h8, op.bl[n]);
-            if constexpr (kAcc1) {
-              const h8 wm = __builtin_bit_cast(h8, op.bm[n]);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, op.ah[m], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, op.ah[m], acc[m][n], 0, 0, 0);
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wm, op.al[m], acc[m][n], 0, 0, 0);
-            } else {
-              acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, op.ah[m], acc[m][n], 0, 0, 0);
-              cor[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, op.ah[m], cor[m][n], 0, 0, 0);
-              cor[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, op.al[m], cor[m][n], 0, 0, 0);
-            }
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, op.ah[m], acc[m][n], 0, 0, 0);
+            cor[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, op.ah[m], cor[m][n], 0, 0, 0);
+            cor[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, op.al[m], cor[m][n], 0, 0, 0);
           }
       };
-      // order pins inside a half-step (kSched 0) and the interleave pattern closing it (kSched 2)
-      auto pin = [&]() {
-        if constexpr (kSched == 0) __builtin_amdgcn_sched_barrier(0);
-      };
-      auto close = [&]() {
-        if constexpr (kSched == 2) {
-#pragma unroll
-          for (int i = 0; i < 3 * WM * WN; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x120, 1, 0);  // then one DS or VMEM read
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      };
+      // order pins inside a half-step (loads, then MFMAs) and closing it
+      auto pin = [&]() { __builtin_amdgcn_sched_barrier(0); };
+      auto close = [&]() { __builtin_amdgcn_sched_barrier(0); };
       auto half_plain = [&](int q, const Ops& use, Ops& nxt_ops) {
         load(q + 1 < nq ? q + 1 : nq - 1, nxt_ops);
         pin();
-        TR(1);
         mfmas(use);
         close();
-        TR(2);
       };
       int staged = 0;
       Ops S0, S1;
@@ -462,18 +360,13 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         Stage st;
         fetch(stid + staged * NTS, s_tile, s_ch, st);
         pin();
-        TR(1);
         mfmas(S0);
         close();
-        TR(2);
         load(q + 2 < nq ? q + 2 : nq - 1, S0);
         pin();
-        TR(1);
         mfmas(S1);
         close();
-        TR(2);
         store(nxt, st);
-        TR(3);
         q += 2;
         for (int r = 1; r < spread; ++r, q += 2) {
           half_plain(q, S0, S1);
@@ -485,7 +378,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         half_plain(q + 1, S1, S0);
       }
       if (nq & 1) mfmas(S0);
-      TR(2);
       if (stage_next) {
         for (int qs = staged; qs < nstage; ++qs) {
           Stage st;
@@ -496,7 +388,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
       if (ch == 0 && tid == 0) squeue[(k + 2) & 3] = taken;
       __syncthreads();
       buf ^= 1;
-      TR(4);
     }
 
     // epilogue of this tile (its global stores drain while the next tile's k-loop runs).
@@ -545,7 +436,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int r = 4 * g + i;
-              const float tv = fmaf(cor[kAcc1 ? 0 : m][kAcc1 ? 0 : n][r], kAcc1 ? 0.f : a.osc_c, fmaf(acc[m][n][r], a.osc, bb[i]));
+              const float tv = fmaf(cor[m][n][r], a.osc_c, fmaf(acc[m][n][r], a.osc, bb[i]));
               yv[r] = fmaxf(tv, tv * a.act_slope) + rr4[i];
             }
           }
@@ -575,7 +466,6 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, make_float4(o[0], o[1], o[2], o[3])), ry, so, 0, 0);
         }
       }
-      TR(5);
       continue;
     }
     // residual: the 4 groups of output tile t+1 are loaded before tile t is finished and stored,
@@ -614,8 +504,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
       if (a.pt) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-          const float bv = kAcc1 ? acc[m][n][8 + r] * a.osc
-                                 : fmaf(cor[kAcc1 ? 0 : m][kAcc1 ? 0 : n][8 + r], a.osc_c, acc[m][n][8 + r] * a.osc);
+          const float bv = fmaf(cor[m][n][8 + r], a.osc_c, acc[m][n][8 + r] * a.osc);
           sh[r] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(((lane + 1) & 63) * 4, __builtin_bit_cast(int, bv)));
         }
       }
@@ -631,8 +520,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * g + i;
-          float tv = kAcc1 ? fmaf(acc[m][n][r], a.osc, bb[i])
-                           : fmaf(cor[kAcc1 ? 0 : m][kAcc1 ? 0 : n][r], a.osc_c, fmaf(acc[m][n][r], a.osc, bb[i]));
+          float tv = fmaf(cor[m][n][r], a.osc_c, fmaf(acc[m][n][r], a.osc, bb[i]));
           if (a.pt && g < 2) tv += sh[r];
           v[i] = fmaxf(tv, tv * a.act_slope);
         }
@@ -646,7 +534,7 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         }
         const unsigned so = (row_ok && j0 < a.coutp) ? vo + 32u * g : kOob;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, make_float4(v[0], v[1], v[2], v[3])),
-                                               ry, so, 0, FVC_STORE_AUX);
+                                               ry, so, 0, 0);
         if constexpr (POST == kPostPool) {
           if (m == 0) {
 #pragma unroll
@@ -682,23 +570,8 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
         }
       }
     }
-    TR(5);
   }
   if (!(mx < 65000.f) && a.ovf) atomicOr(a.ovf, 1);
-#if FVC_X3_TRACE
-  {
-    const unsigned long long tr_end = x3_stamp();
-    tr[6] = tr_end - tr_begin;
-    tr[7] = 1;
-    const unsigned slot = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * NWV + wave;
-    if (lane < kTraceVals && slot < (unsigned)kTraceSlots) {
-      unsigned long long v = tr[0];
-#pragma unroll
-      for (int i = 1; i < kTraceVals; ++i) v = lane == i ? tr[i] : v;
-      atomicAdd(&g_x3_trace[(size_t)slot * kTraceVals + lane], v);
-    }
-  }
-#endif
   finish();
 }
 
@@ -964,18 +837,6 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
 
 extern "C" {
 
-#if FVC_X3_TRACE
-// diagnostic builds: copy (and clear) the per-wave segment sums [slot][8]
-int fvc_x3_trace_read(unsigned long long* host, int nslots) {
-  if (nslots > kTraceSlots) nslots = kTraceSlots;
-  if (hipDeviceSynchronize() != hipSuccess) return FVC_EINVAL;
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_x3_trace), (size_t)nslots * kTraceVals * 8) != hipSuccess) return FVC_EINVAL;
-  static unsigned long long zeros[kTraceSlots * kTraceVals];
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_x3_trace), zeros, sizeof(zeros)) != hipSuccess) return FVC_EINVAL;
-  return 0;
-}
-#endif
-
 int fvc_conv_x3_supported(int cin, int cout, int ksize, int stride, int transposed) {
   X3Cfg c;
   return x3_cfg(cin, cout, ksize, stride, transposed, c) ? 1 : 0;
@@ -1053,14 +914,7 @@ int fvc_conv_x3_pack_weight(const float* w, void* wp, float* osc_out, int cin, i
               if (ci >= cin) continue;
               const float v = (transposed ? w[(((size_t)ci * cout + jo) * ks + ky) * ks + kx]
                                           : w[(((size_t)jo * cin + ci) * ks + ky) * ks + kx]) * sc;
-              if (kAcc1) {
-                const _Float16 hi = (_Float16)v;
-                out[frag + e] = hi;                                                 // plane 0: hi
-                out[frag + 64 * 8 + e] = (_Float16)(v - (float)hi);                 // plane 1: w - hi
-                out[frag + 128 * 8 + e] = (_Float16)((float)hi * (1.f / 2048.f));  // plane 2: hi 2^-11
-              } else {
-                fvc_split_store(out + frag + e, out + frag + 64 * 8 + e, v);  // planes 0 (lanes 0..63), 1
-              }
+              fvc_split_store(out + frag + e, out + frag + 64 * 8 + e, v);  // planes 0 (lanes 0..63), 1
             }
           }
   return 0;

@@ -12,12 +12,6 @@
 #include "fvc_common.h"
 #include <math.h>
 
-// cache policy of the activation stores (aux operand of buffer_store; experiment builds only,
-// e.g. 2 = non-temporal on gfx950)
-#ifndef FVC_STORE_AUX
-#define FVC_STORE_AUX 0
-#endif
-
 // ---------------------------------------------------------------------------------- device side
 // The kernel files pull these in with `using namespace fvc_split;` inside their own namespace.
 namespace fvc_split {
@@ -32,7 +26,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr;
 // Accumulation: two weight planes (hi, lo*2^11) and activations split as hi + lo*2^-11; the
 // correction products go to a second accumulator scaled by 2^-11 at the end. (Measured and
 // rejected, r2: one accumulator with UNSCALED residual halves -- 64 fewer VGPRs, same speed on
-// every geometry (scripts/gpu_x3_variants.sh), but an activation residual below 2^-14 is an
+// every geometry (profiles/r2/x3_experiments), but an activation residual below 2^-14 is an
 // fp16 subnormal and small-activation layers lose accuracy: 4.8e-4 relative at |x| ~ 1e-4.)
 constexpr float kLoScale = 2048.f;
 

@@ -1,7 +1,7 @@
 """Micro-benchmark of mvDecoder deconv7 -> deconv8 as the bench runs it: the stride-2 transposed
 3x3 128->128 conv on conv_dx_kernel with deconv8's (3x3 128->2) tap partials in its epilogue
-(synthesis_mv.py:41-43), at 544x960 -> 1088x1920, then the tap gather. FVC_LIB_PATH selects an
-experiment library (e.g. a -DFVC_DX_KO knock-out build)."""
+(synthesis_mv.py:41-43), at 544x960 -> 1088x1920, then the tap gather. FVC_LIB_PATH selects another
+build's library (A/B)."""
 import argparse
 import os
 import sys

@@ -1,5 +1,6 @@
 #!/bin/bash
-# Pipelined bench A/B of libfvc builds: each argument is a variant suffix ("base" = libfvc.so);
+# Pipelined bench A/B of libfvc builds: each argument names a library fastvideocodec_amd/libfvc_<arg>.so
+# (a copy of another commit's build; "base" = libfvc.so);
 # runs bench.py (no CPU leg) per library, twice in alternation, and prints value lines.
 export TMPDIR=/tmp
 TAG=${TAG:-bab}

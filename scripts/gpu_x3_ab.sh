@@ -1,6 +1,6 @@
 #!/bin/bash
-# A/B of conv_x3 builds x launch options: each argument "name:lib:VAR=V,VAR2=V2" (lib = variant
-# library suffix or "base" for libfvc.so, vars optional) runs conv_micro at batch 4; then, unless
+# A/B of conv_x3 builds x launch options: each argument "name:lib:VAR=V,VAR2=V2" (lib = suffix of a
+# copy of another commit's build, libfvc_<lib>.so, or "base" for libfvc.so, vars optional) runs conv_micro at batch 4; then, unless
 # NOTEST is set, the conv parity tests under each spec.
 export TMPDIR=/tmp
 TAG=${TAG:-ab}

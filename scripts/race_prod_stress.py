@@ -2,8 +2,9 @@
 (profiles/r6/race/README.md)? Stream A runs one production conv geometry back to back at 4K; stream B
 runs the production motion-compensation warp (fvc_mc_assemble) on fixed inputs and compares every
 output with a golden one made while stream A was idle (a device-side count, no host sync per
-launch). Prints the mismatching pixel count per antagonist. FVC_LIB_PATH=.../libfvc_k7.so adds the
-7x7 8->32 layer on the stem kernel (the experiment that shows the fault) as a positive control."""
+launch). Prints the mismatching pixel count per antagonist. FVC_LIB_PATH selects another build's
+library (r6's positive control was one with the 7x7 8->32 layer on the stem kernel, the experiment
+that shows the fault)."""
 import os
 import sys
 
@@ -17,7 +18,7 @@ H, W = 2176, 3840
 ITERS = int(os.environ.get("ITERS", "40"))
 # (name, cin, cout, k, stride, transposed, h, w, in_op, act): every split family's production shapes
 CASES = [
-    ("7x7 8->32 (x3; the stem in a K7 lib)", 8, 32, 7, 1, False, H, W, K.IN_NONE, K.ACT_RELU),
+    ("7x7 8->32 (x3)", 8, 32, 7, 1, False, H, W, K.IN_NONE, K.ACT_RELU),
     ("f32 7x7 16->2", 16, 2, 7, 1, False, H, W, K.IN_NONE, K.ACT_NONE),
     ("x3 3x3 s2 128->128", 128, 128, 3, 2, False, H // 2, W // 2, K.IN_NONE, K.ACT_LRELU),
     ("wino 3x3 64->64", 64, 64, 3, 1, False, H, W, K.IN_RELU, K.ACT_RELU),

@@ -1,13 +1,14 @@
 // r6: standalone reproducer for the K7-stem / warp-gather hazard (profiles/r6/race/README.md).
-// No torch, no pipeline: two HIP streams and two C-ABI entry points of an experiment build of
-// libfvc (-DFVC_STEM_K7, which puts SpyNet's 7x7 8 -> 32 layer on conv_stem_kernel).
+// No torch, no pipeline: two HIP streams and two C-ABI entry points of libfvc. The stem antagonist
+// needs a library whose conv_stem_kernel takes SpyNet's 7x7 8 -> 32 layer (a build of commit 1efa56a
+// or earlier with its 7x7 stem switch); the synthetic antagonists run against any libfvc.so.
 //   stream A: fvc_conv2d_nhwc_stem 7x7 8->32 over a 5-level pyramid (the SpyNet launch pattern)
 //   stream B: fvc_mc_assemble (k_mc_assemble_q: bilinear 4-tap gathers, two pixels per thread) on
 //             fixed inputs, then a compare kernel against a golden output made with stream A idle
 // Every mismatching pixel is counted by wave-lane quarter and by which of the thread's pixels
 // (first / second of its pair) it is.
 // build: hipcc --offload-arch=gfx950 -O2 -Iinclude scripts/race_repro.hip -o gpurun_out/race_repro \
-//          -Lfastvideocodec_amd -l:libfvc_k7.so -Wl,-rpath,$PWD/fastvideocodec_amd
+//          -Lfastvideocodec_amd -l:libfvc.so -Wl,-rpath,$PWD/fastvideocodec_amd
 // run:   gpurun_out/race_repro ITERS ANTAGONIST VICTIM
 //   ANTAGONIST 0 none, 1 the library's 7x7 stem (fvc_conv2d_nhwc_stem), else a synthetic persistent
 //              kernel (k_antagonist) given as MF,LDSREAD,LDS_BYTES,LO,SPAN, e.g. 1,1,85376,0,85360 =
@@ -189,7 +190,7 @@ int main(int argc, char** argv) {
   // ---- the 7x7 8 -> 32 stem over five pyramid levels
   const int cin = 8, cout = 32, k = 7;
   if (use_stem && !fvc_conv_stem_supported(cin, cout, k, 1, 0)) {
-    fprintf(stderr, "this library has no 7x7 stem (build with -DFVC_STEM_K7)\n");
+    fprintf(stderr, "this library has no 7x7 stem (the product keeps that layer on x3)\n");
     return 2;
   }
   std::vector<float> w((size_t)cout * cin * k * k), bias(cout);

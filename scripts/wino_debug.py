@@ -1,5 +1,5 @@
 """Tiny Winograd-kernel cases against a float64 conv, with the error's location (debug aid).
-   FVC_LIB_PATH selects an experiment library."""
+   FVC_LIB_PATH selects another build's library."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

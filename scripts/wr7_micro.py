@@ -1,6 +1,6 @@
 """Time the Winograd-rows 7x7 conv alone (SpyNet level-4 layers at 1088x1920, 16 frames per
 launch, as the bench batches them) against the direct split kernel: algorithmic TF/s per layer.
-Libraries: FVC_LIB_PATH selects an experiment build (python -m fastvideocodec_amd.build --variant)."""
+FVC_LIB_PATH selects another build's library (A/B)."""
 import os
 import sys
 
