@@ -857,35 +857,34 @@ static int wino_launch_pre(const WinoArgs& a, int act, hipStream_t s, int grid) 
   return wino_launch4<IOP, 0, kResPre, FVC_ACT_LRELU>(a, grid, s);
 }
 
-// pitch = 128: x / y / res point at the first channel of a 64-channel half of 128-channel tensors;
-// res_pre adds res before the activation (bias may then be null: zeros)
-static int run_wino(const float* x, const void* upack, float osc, const float* bias, const float* res, float* y,
-                    float* pool, int batch, int h, int w, int in_op, int act, int cu_reserve, int* ovf, int* sched,
-                    int sched_len, hipStream_t s, const void* tw = nullptr, float tosc = 0.f, int pcp = 0,
-                    int pitch = kC, bool res_pre = false, const float* xl = nullptr, float* xu = nullptr) {
-  if (tw && (pool || in_op != FVC_IN_NONE || pcp <= 0 || pcp > 32 || (pcp & 3))) return FVC_EINVAL;
-  // UP: x is the skip S, xl the half-resolution source, xu receives S + up2(xl)
-  if ((xl != nullptr) != (xu != nullptr)) return FVC_EINVAL;
-  if (xl && (tw || pool || res || pitch != kC || (h & 1) || (w & 1))) return FVC_EINVAL;
-  if (!x || !upack || (!bias && pitch == kC) || !y || batch <= 0 || h <= 0 || w <= 0 || cu_reserve < 0 ||
-      sched_len < 0)
+// What a call is beyond the plain 64 -> 64 conv. pitch = 128: x / y / res point at the first
+// channel of a 64-channel half of 128-channel tensors; res_pre adds res before the activation
+// (bias may then be null: zeros); UP: x is the skip S, xl the half-resolution source, xu
+// receives S + up2(xl).
+struct WinoForm {
+  int pitch = kC;
+  bool res_pre = false;
+  const float* xl = nullptr;
+  float* xu = nullptr;
+};
+
+static int run_wino(const FvcConvCall& c, const WinoForm& f = {}) {
+  const int h = c.h, w = c.w, in_op = c.in_op, act = c.act, pitch = f.pitch;
+  const void* const tw = c.tw;
+  if (tw && (c.pool || in_op != FVC_IN_NONE || c.pcp <= 0 || c.pcp > 32 || (c.pcp & 3))) return FVC_EINVAL;
+  if ((f.xl != nullptr) != (f.xu != nullptr)) return FVC_EINVAL;
+  if (f.xl && (tw || c.pool || c.res || pitch != kC || (h & 1) || (w & 1))) return FVC_EINVAL;
+  if (!c.x || !c.wpack || (!c.bias && pitch == kC) || !c.y || c.batch <= 0 || h <= 0 || w <= 0 || !fvc_tail_ok(c.tail))
     return FVC_EINVAL;
-  if (pitch != kC && (pitch != 2 * kC || tw || pool)) return FVC_EINVAL;
-  if (res_pre && (!res || pitch != 2 * kC)) return FVC_EINVAL;
+  if (pitch != kC && (pitch != 2 * kC || tw || c.pool)) return FVC_EINVAL;
+  if (f.res_pre && (!c.res || pitch != 2 * kC)) return FVC_EINVAL;
   if (in_op != FVC_IN_NONE && in_op != FVC_IN_RELU) return FVC_EINVAL;
   // every buffer descriptor spans one input row or one 2-row output band: 32-bit offsets hold
   // for any batch, only a band must stay below 4 GB
   if ((unsigned long long)w * pitch * 4ull * 2ull >= (1ull << 31)) return FVC_EINVAL;
   WinoArgs a;
-  a.x = x;
-  a.u = (const uint4*)upack;
-  a.bias = bias;
-  a.res = res;
-  a.y = y;
-  a.pool = pool;
-  a.B = batch;
-  a.H = h;
-  a.W = w;
+  a.x = c.x; a.u = (const uint4*)c.wpack; a.bias = c.bias; a.res = c.res; a.y = c.y; a.pool = c.pool;
+  a.B = c.batch; a.H = h; a.W = w;
   a.tiles_y = (h + 1) / 2;
   a.ngroups = fvc_cdiv(w, 32);
   // 16 tile rows per chunk. Longer chunks re-stage fewer halo rows (a chunk's first item stages 4
@@ -893,36 +892,30 @@ static int run_wino(const float* x, const void* upack, float osc, const float* b
   // on the 272x480 quarters (profiles/r6/wino_ko/chunk.txt). The result does not depend on it.
   a.chunk = kChunk;
   a.chunks_per_col = fvc_cdiv(a.tiles_y, a.chunk);
-  a.nchunks = batch * a.ngroups * a.chunks_per_col;
-  a.osc = osc;
-  a.osc_c = fvc_lo_scale(osc);
-  a.ovf = ovf;
-  a.tw = (const uint4*)tw;
-  a.tosc = tosc;
-  a.tosc_c = fvc_lo_scale(tosc);
-  a.pcp = pcp;
+  a.nchunks = c.batch * a.ngroups * a.chunks_per_col;
+  a.osc = c.osc; a.osc_c = fvc_lo_scale(c.osc);
+  a.ovf = c.tail.ovf;
+  a.tw = (const uint4*)tw; a.tosc = c.tosc; a.tosc_c = fvc_lo_scale(c.tosc); a.pcp = c.pcp;
   a.xp = a.yp = pitch;
-  a.xl = xl;
-  a.xu = xu;
-  a.hl = h / 2;
-  a.wl = w / 2;
+  a.xl = f.xl; a.xu = f.xu; a.hl = h / 2; a.wl = w / 2;
   // ATen's align_corners=True scale (in - 1) / (out - 1), as k_up2_add_q16p computes it
   a.usy = h > 1 ? (float)(a.hl - 1) / (float)(h - 1) : 0.f;
   a.usx = w > 1 ? (float)(a.wl - 1) / (float)(w - 1) : 0.f;
-  const int ncu = fvc_persistent_cus(cu_reserve);
+  const int ncu = fvc_persistent_cus(c.tail.cu_reserve);
   int grid = ncu < a.nchunks ? ncu : a.nchunks;
-  a.sched = fvc_dyn_sched(sched, sched_len, 2);
+  a.sched = fvc_dyn_sched(c.tail.sched, c.tail.sched_len, 2);
+  const hipStream_t s = c.tail.stream;
   if (act != FVC_ACT_NONE && act != FVC_ACT_RELU && act != FVC_ACT_LRELU) return FVC_EINVAL;
   if (tw) return wino_launch<FVC_IN_NONE, kPostTap>(a, act, s, grid);
-  if (xl) {
+  if (f.xl) {
     if (in_op == FVC_IN_NONE) return wino_launch_up<FVC_IN_NONE>(a, act, s, grid);
     return wino_launch_up<FVC_IN_RELU>(a, act, s, grid);
   }
-  if (res_pre) {
+  if (f.res_pre) {
     if (in_op == FVC_IN_NONE) return wino_launch_pre<FVC_IN_NONE>(a, act, s, grid);
     return wino_launch_pre<FVC_IN_RELU>(a, act, s, grid);
   }
-  if (pool) {
+  if (c.pool) {
     if (in_op == FVC_IN_NONE) return wino_launch<FVC_IN_NONE, kPostPool>(a, act, s, grid);
     return wino_launch<FVC_IN_RELU, kPostPool>(a, act, s, grid);
   }
@@ -1010,8 +1003,9 @@ int fvc_conv2d_nhwc_wino_tap(const float* x, const void* wpack, float osc, const
                              float* P, int batch, int h, int w, int act, const void* tap_wpack, float tap_osc, int pcp,
                              int cu_reserve, int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
   if (!tap_wpack) return FVC_EINVAL;
-  return run_wino(x, wpack, osc, bias, res, P, nullptr, batch, h, w, FVC_IN_NONE, act, cu_reserve, overflow_flag,
-                  sched, sched_len, (hipStream_t)stream, tap_wpack, tap_osc, pcp);
+  FvcConvCall c{x, wpack, osc, bias, res, P, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.act = act; c.tw = tap_wpack; c.tosc = tap_osc; c.pcp = pcp;
+  return run_wino(c);
 }
 
 int fvc_conv_wino128_supported(int cin, int cout, int ksize, int stride, int transposed) {
@@ -1051,15 +1045,22 @@ int fvc_conv2d_nhwc_wino128(const float* x, const void* wpack, const float* osc4
                             int* sched, int sched_len, fvc_stream_t stream) {
   if (!x || !wpack || !osc4 || !bias || !y) return FVC_EINVAL;
   const size_t qb = fvc_conv_wino_wpack_bytes();
+  WinoForm half;  // x / y / res: 64-channel halves of 128-channel tensors
+  half.pitch = 2 * kC;
+  FvcConvCall c{};
+  c.batch = batch; c.h = h; c.w = w; c.in_op = in_op;
+  c.tail = {cu_reserve, overflow_flag, sched, sched_len, stream};
   for (int oh = 0; oh < 2; ++oh) {
-    float* yh = y + kC * oh;
-    int r = run_wino(x, (const char*)wpack + (2 * oh) * qb, osc4[2 * oh], nullptr, nullptr, yh, nullptr, batch, h, w,
-                     in_op, FVC_ACT_NONE, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream, nullptr,
-                     0.f, 0, 2 * kC, false);
+    c.y = y + kC * oh;
+    c.x = x; c.wpack = (const char*)wpack + (2 * oh) * qb; c.osc = osc4[2 * oh];
+    c.bias = nullptr; c.res = nullptr; c.act = FVC_ACT_NONE;
+    half.res_pre = false;
+    int r = run_wino(c, half);
     if (r) return r;
-    r = run_wino(x + kC, (const char*)wpack + (2 * oh + 1) * qb, osc4[2 * oh + 1], bias + kC * oh, yh, yh, nullptr,
-                 batch, h, w, in_op, act, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream, nullptr,
-                 0.f, 0, 2 * kC, true);
+    c.x = x + kC; c.wpack = (const char*)wpack + (2 * oh + 1) * qb; c.osc = osc4[2 * oh + 1];
+    c.bias = bias + kC * oh; c.res = c.y; c.act = act;
+    half.res_pre = true;
+    r = run_wino(c, half);
     if (r) return r;
   }
   return 0;
@@ -1072,15 +1073,20 @@ int fvc_conv2d_nhwc_wino_up(const float* skip, const float* low, float* xsum, co
                             const float* bias, float* y, int batch, int h, int w, int in_op, int act, int cu_reserve,
                             int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
   if (!skip || !low || !xsum) return FVC_EINVAL;
-  return run_wino(skip, wpack, osc, bias, nullptr, y, nullptr, batch, h, w, in_op, act, cu_reserve, overflow_flag,
-                  sched, sched_len, (hipStream_t)stream, nullptr, 0.f, 0, kC, false, low, xsum);
+  FvcConvCall c{skip, wpack, osc, bias, /*res*/ nullptr, y, batch, h, w,
+                {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.in_op = in_op; c.act = act;
+  WinoForm up;
+  up.xl = low; up.xu = xsum;
+  return run_wino(c, up);
 }
 
 int fvc_conv2d_nhwc_wino(const float* x, const void* wpack, float osc, const float* bias, const float* res,
                          float* y, float* pool, int batch, int h, int w, int in_op, int act, int cu_reserve,
                          int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
-  return run_wino(x, wpack, osc, bias, res, y, pool, batch, h, w, in_op, act, cu_reserve, overflow_flag, sched,
-                  sched_len, (hipStream_t)stream);
+  FvcConvCall c{x, wpack, osc, bias, res, y, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.in_op = in_op; c.act = act; c.pool = pool;
+  return run_wino(c);
 }
 
 }  // extern "C"

@@ -576,8 +576,9 @@ int fvc_conv_wr7_pack_weight(const float* w, int cin, int cout, int ci0, int co0
 int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float osc, const float* bias, float* y,
                         int yp, int batch, int h, int w, int mode, int act, int cu_reserve, int* overflow_flag,
                         int* sched, int sched_len, fvc_stream_t stream) {
-  if (!x || !upack || !y || (nt != 1 && nt != 2) || batch <= 0 || h <= 0 || w <= 0 || cu_reserve < 0 ||
-      sched_len < 0 || mode < 0 || mode > 2 || (mode != kModePartial && !bias))
+  const FvcTail tail{cu_reserve, overflow_flag, sched, sched_len, stream};
+  if (!x || !upack || !y || (nt != 1 && nt != 2) || batch <= 0 || h <= 0 || w <= 0 || !fvc_tail_ok(tail) || mode < 0 ||
+      mode > 2 || (mode != kModePartial && !bias))
     return FVC_EINVAL;
   if (act != FVC_ACT_NONE && act != FVC_ACT_RELU && act != FVC_ACT_LRELU) return FVC_EINVAL;
   if (xp < kCi || (xp & 3) || yp < 16 * nt || (yp & 3)) return FVC_EINVAL;
@@ -594,7 +595,7 @@ int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float
   a.xp = xp;
   a.yp = yp;
   a.ngroups = fvc_cdiv(w, 32);
-  const int ncu = fvc_persistent_cus(cu_reserve);
+  const int ncu = fvc_persistent_cus(tail.cu_reserve);
   a.rows = wr7_rows(batch, h, a.ngroups, ncu);
   a.chunks_per_col = fvc_cdiv(h, a.rows);
   const long long nch = (long long)batch * a.ngroups * a.chunks_per_col;
@@ -602,11 +603,11 @@ int fvc_conv2d_nhwc_wr7(const float* x, int xp, const void* upack, int nt, float
   a.nchunks = (int)nch;
   a.osc = osc;
   a.osc_c = fvc_lo_scale(osc);
-  a.ovf = overflow_flag;
+  a.ovf = tail.ovf;
   const int grid = ncu < a.nchunks ? ncu : a.nchunks;
-  a.sched = fvc_dyn_sched(sched, sched_len, 2);
-  if (nt == 2) return wr7_launch1<2>(a, mode, act, grid, (hipStream_t)stream);
-  return wr7_launch1<1>(a, mode, act, grid, (hipStream_t)stream);
+  a.sched = fvc_dyn_sched(tail.sched, tail.sched_len, 2);
+  if (nt == 2) return wr7_launch1<2>(a, mode, act, grid, tail.stream);
+  return wr7_launch1<1>(a, mode, act, grid, tail.stream);
 }
 
 }  // extern "C"

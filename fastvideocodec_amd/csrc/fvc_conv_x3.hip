@@ -576,13 +576,11 @@ __global__ __launch_bounds__(NWV * 64) void conv_x3_kernel(const X3Args a) {
 }
 
 // ------------------------------------------------------------------ host-side geometry
-struct X3Cfg : FvcTaps {
-  int cinp, coutp, ntp, cc, wm, wn, nw, nchunks, th;
+// th / nks / wcls / wtotal (fvc_dx::Plan) describe the direct kernel's tile and pack as well
+struct X3Cfg : FvcTaps, fvc_dx::Plan {
+  int cinp, coutp, ntp, cc, wm, wn, nw, nchunks;
   int pt;     // pair-tap form (16 output channels, stride 1): (ky, even kx) pairs, see X3Args::pt
   int dx;     // stride-2 transposed conv on fvc_deconv_x3.hip (all classes per staged tile, one chunk)
-  int nks[4];
-  long long wcls[4];
-  long long wtotal;  // uint4 (16-B) units
 };
 static_assert(kMaxTapsX == kFvcMaxTaps, "X3Args and FvcTaps hold the same tap lists");
 
@@ -615,7 +613,7 @@ static bool x3_cfg(int cin, int cout, int ks, int stride, int transposed, X3Cfg&
   c.pt = (!transposed && stride == 1 && c.coutp == 16 && ks >= 3 && fvc_env_int("FVC_X3_PT", 1)) ? 1 : 0;
   if (!fvc_taps(ks, stride, transposed, c.pt, c)) return false;
   // the all-classes kernel where it takes the layer; its pack is this pack with one channel chunk
-  c.dx = fvc_dx::config(c, c.cinp, c.ntp, kFrag, c.th, c.nks, c.wcls, c.wtotal) ? 1 : 0;
+  c.dx = fvc_dx::config(c, c.cinp, c.ntp, kFrag, c) ? 1 : 0;
   if (c.dx) {
     c.cc = c.cinp;
     c.nchunks = 1;
@@ -701,19 +699,31 @@ static int x3_launch_cc(int nwv, int wm, int wn, int iop, int post, const X3Args
   return FVC_EINVAL;
 }
 
-// tw != null: fused tap epilogue (y receives P [batch][Ho][Wo][pcp], see kPostTap)
-static int run_x3(const float* x, const void* wpack, float osc, const float* bias, const float* res,
-                  float* y, int batch, int h, int w, int cin, int cout, int ks, int stride, int transposed,
-                  int in_op, int act, int post_op, int cu_reserve, int* ovf, int* sched, int sched_len,
-                  hipStream_t s, const void* tw = nullptr, float tosc = 0.f, int pcp = 0, float* pool = nullptr) {
+// call for images [b0, b1) alone: x, y, res and pool advance by b0 images of their own sizes
+// (ych = channels of the tensor y points to)
+static FvcConvCall x3_images(FvcConvCall call, const X3Cfg& c, const X3Args& a, int ych, int b0, int b1) {
+  call.batch = b1 - b0;
+  call.x += b0 * ((size_t)a.H * a.W * c.cinp);
+  call.y += b0 * ((size_t)a.Ho * a.Wo * ych);
+  if (call.res) call.res += b0 * ((size_t)a.Ho * a.Wo * c.coutp);
+  if (call.pool) call.pool += b0 * ((size_t)(a.Ho / 2) * (a.Wo / 2) * c.coutp);
+  return call;
+}
+
+// call.tw != null: fused tap epilogue (y receives P [batch][Ho][Wo][pcp], see kPostTap)
+static int run_x3(const FvcConvGeom& g, const FvcConvCall& call) {
+  const bool tap = call.tw != nullptr, pool = call.pool != nullptr;
+  const int batch = call.batch, h = call.h, w = call.w, in_op = call.in_op;
+  int post_op = call.post_op;  // the kernel's: kPostTap / kPostPool for the fused forms
+  if (!fvc_tail_ok(call.tail)) return FVC_EINVAL;
   X3Cfg c;
-  if (!x3_cfg(cin, cout, ks, stride, transposed, c)) return FVC_EINVAL;
-  if (!x || !wpack || !bias || !y || batch <= 0) return FVC_EINVAL;
-  if (tw) {
+  if (!x3_cfg(g.cin, g.cout, g.ksize, g.stride, g.transposed, c)) return FVC_EINVAL;
+  if (!call.x || !call.wpack || !call.bias || !call.y || batch <= 0) return FVC_EINVAL;
+  if (tap) {
     // every output channel in one wave: N-tiles 1, 2 (2 strips per wave) or 4 (1 strip); the
     // channel chunk (and so the weight pack) stays what x3_cfg chose: fewer strips only shrink LDS
-    if (post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.ntp == 3 || c.ntp > 4 || pcp <= 0 ||
-        pcp > 32 || (pcp & 3) || (c.dx && c.ntp != 4))
+    if (post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.ntp == 3 || c.ntp > 4 || call.pcp <= 0 ||
+        call.pcp > 32 || (call.pcp & 3) || (c.dx && c.ntp != 4))
       return FVC_EINVAL;
     if (!c.dx) {
       if (c.ntp == 4) c.wm = 1;
@@ -723,49 +733,41 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   }
   if (pool) {
     // y and avg_pool2d(y): stride-1 conv, two strips per wave (rows 2r, 2r + 1), one N-group
-    if (tw || transposed || stride != 1 || post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.wm != 2 || c.ntp > 2)
+    if (tap || g.transposed || g.stride != 1 || post_op != FVC_POST_NONE || in_op != FVC_IN_NONE || c.wm != 2 ||
+        c.ntp > 2)
       return FVC_EINVAL;
     post_op = kPostPool;
   }
-  const int ych = tw ? pcp : c.coutp;  // channels of the tensor y points to
+  const int ych = tap ? call.pcp : c.coutp;  // channels of the tensor y points to
   X3Args a;
-  a.x = x; a.w = (const uint4*)wpack; a.bias = bias; a.res = res; a.y = y;
-  a.tw = (const uint4*)tw; a.pcp = pcp;
-  a.tosc = tosc; a.tosc_c = fvc_lo_scale(tosc);
+  a.x = call.x; a.w = (const uint4*)call.wpack; a.bias = call.bias; a.res = call.res; a.y = call.y;
+  a.tw = (const uint4*)call.tw; a.pcp = call.pcp;
+  a.tosc = call.tosc; a.tosc_c = fvc_lo_scale(call.tosc);
   a.B = batch; a.H = h; a.W = w; a.cinp = c.cinp;
-  a.coutp = c.coutp; a.cout = cout;
-  if (!fvc_out_dims(h, w, stride, transposed, a.Ho, a.Wo, a.Hq, a.Wq)) return FVC_EINVAL;
+  a.coutp = c.coutp; a.cout = g.cout;
+  if (!fvc_out_dims(h, w, g.stride, g.transposed, a.Ho, a.Wo, a.Hq, a.Wq)) return FVC_EINVAL;
   // y and res are addressed through buffer descriptors with 32-bit offsets: split batches whose
   // output tensor reaches 4 GB into launches over sub-batches
   const unsigned long long ybytes = (unsigned long long)batch * a.Ho * a.Wo * ych * 4ull;
   const unsigned long long rbytes = (unsigned long long)batch * a.Ho * a.Wo * a.coutp * 4ull;
   const long long split_env = fvc_env_int("FVC_X3_SPLIT_BYTES", 0);  // tests: force the split path
   const unsigned long long split_at = split_env > 0 ? (unsigned long long)split_env : (1ull << 32) - 4096;
-  if (ybytes >= split_at || (res && rbytes >= split_at)) {
+  if (ybytes >= split_at || (call.res && rbytes >= split_at)) {
     if (batch == 1) return FVC_EINVAL;
-    const int b1 = batch / 2;
-    const size_t xs = (size_t)h * w * c.cinp, ys = (size_t)a.Ho * a.Wo * ych, rs = (size_t)a.Ho * a.Wo * c.coutp;
-    const int post_in = (tw || pool) ? FVC_POST_NONE : post_op;
-    const size_t pls = (size_t)(a.Ho / 2) * (a.Wo / 2) * c.coutp;
-    int rc = run_x3(x, wpack, osc, bias, res, y, b1, h, w, cin, cout, ks, stride, transposed, in_op, act,
-                    post_in, cu_reserve, ovf, sched, sched_len, s, tw, tosc, pcp, pool);
-    if (rc) return rc;
-    return run_x3(x + b1 * xs, wpack, osc, bias, res ? res + b1 * rs : nullptr, y + b1 * ys, batch - b1, h, w, cin, cout, ks,
-                  stride, transposed, in_op, act, post_in, cu_reserve, ovf, sched, sched_len, s, tw, tosc, pcp,
-                  pool ? pool + b1 * pls : nullptr);
+    // the halves carry the caller's post_op (none in the tap and pool forms), not the kernel's
+    const int rc = run_x3(g, x3_images(call, c, a, ych, 0, batch / 2));
+    return rc ? rc : run_x3(g, x3_images(call, c, a, ych, batch / 2, batch));
   }
   a.y_bytes = (unsigned)ybytes;
   a.res_bytes = (unsigned)rbytes;
-  a.pool = pool;
+  a.pool = call.pool;
   a.pool_bytes = (unsigned)((unsigned long long)batch * (a.Ho / 2) * (a.Wo / 2) * c.coutp * 4ull);
   // the input is addressed per image (blockIdx.z) through a 32-bit-range descriptor too
   const unsigned long long xbytes = (unsigned long long)h * w * c.cinp * 4ull;
   if (xbytes >= (1ull << 32) - 4096) return FVC_EINVAL;
   a.x_bytes = (unsigned)xbytes;
-  a.ovf = ovf;
-  if (c.dx)
-    return fvc_dx::run(c, c.cinp, c.coutp, c.ntp, c.th, c.nks, c.wcls, x, wpack, osc, bias, res, y, batch, h, w, cout,
-                       in_op, act, post_op, cu_reserve, ovf, sched, sched_len, s, tw, tosc, pcp, a.y_bytes, a.x_bytes);
+  a.ovf = call.tail.ovf;
+  if (c.dx) return fvc_dx::run(c, c.cinp, c.coutp, c.ntp, g.cout, c, call, a.y_bytes, a.x_bytes);
   a.sin = c.sin; a.sout = c.sout; a.nclass = c.nclass; a.nchunks = c.nchunks; a.ntp = c.ntp;
   a.dymin = c.dymin; a.dxmin = c.dxmin;
   const int th = c.th;
@@ -773,13 +775,13 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   a.xcd = fvc_env_int("FVC_X3_XCD", 1) ? 1 : 0;
   a.ic = 31 * c.sin + 1 + (c.dxmax - c.dxmin);
   a.pt = c.pt;
-  if (c.pt && (tw || pool)) return FVC_EINVAL;
+  if (c.pt && (tap || pool)) return FVC_EINVAL;
   a.half = c.sin == 2 ? (a.ic + 1) / 2 : 0;
   a.inv_ic = 1.0f / (float)a.ic;
-  a.act_slope = fvc_act_slope(act);
-  a.in_op = in_op; a.act = act; a.post_op = post_op;
-  a.osc = osc;
-  a.osc_c = fvc_lo_scale(osc);
+  a.act_slope = fvc_act_slope(call.act);
+  a.in_op = in_op; a.act = call.act; a.post_op = post_op;
+  a.osc = call.osc;
+  a.osc_c = fvc_lo_scale(call.osc);
   for (int cl = 0; cl < 4; ++cl) {
     const bool v = cl < c.nclass;
     a.nks[cl] = v ? c.nks[cl] : 0;
@@ -807,24 +809,25 @@ static int run_x3(const float* x, const void* wpack, float osc, const float* bia
   // has too few spatial tiles x N-groups to give every CU of the persistent grid some work
   // stride-2 convs (one strip per wave) with 4 N-tiles take all 128 channels per block: the
   // input tile is staged once instead of twice (3x3 s2 128->128 at 544x960: 0.214 -> 0.191 ms)
-  int wn = (c.wm == 1 && !transposed && stride == 2 && c.ntp % 4 == 0) ? 4 : (c.ntp >= 2 ? 2 : 1);
-  const int want_wn = (tw || pool) ? c.ntp : fvc_env_int("FVC_X3_WN", 0);
+  int wn = (c.wm == 1 && !g.transposed && g.stride == 2 && c.ntp % 4 == 0) ? 4 : (c.ntp >= 2 ? 2 : 1);
+  const int want_wn = (tap || pool) ? c.ntp : fvc_env_int("FVC_X3_WN", 0);
   if (want_wn == 1 || want_wn == 2 || (want_wn == 4 && c.wm == 1)) wn = want_wn;
   while (wn > 1 && c.ntp % wn) wn >>= 1;
   const long long base = (long long)tiles_x * tiles_y * batch * c.nclass;
   if (!want_wn)
     while (wn > 1 && base * (c.ntp / wn) < 2LL * fvc_num_cus()) wn >>= 1;
-  if ((tw || pool) && wn != c.ntp) return FVC_EINVAL;
+  if ((tap || pool) && wn != c.ntp) return FVC_EINVAL;
   if (lds > 160 * 1024) return FVC_EINVAL;
   // persistent grid: ~one 8-wave block per CU, each walking a contiguous run of spatial tiles
-  const int ncu = fvc_persistent_cus(cu_reserve);
+  const int ncu = fvc_persistent_cus(call.tail.cu_reserve);
   const long long yz = (long long)(c.ntp / wn) * batch;
   long long gx = ((long long)ncu + yz - 1) / yz;  // blocks over all (tile, class) items
   if (gx > (long long)tiles_x * tiles_y * c.nclass) gx = (long long)tiles_x * tiles_y * c.nclass;
   if (gx < 1) gx = 1;
   dim3 grid((unsigned)gx, c.ntp / wn, batch);
   // dynamic schedule when the caller's scratch holds the group counters (FVC_X3_DYN=0: static runs)
-  a.sched = fvc_dyn_sched(sched, sched_len, 1 + (long long)grid.y * grid.z);
+  a.sched = fvc_dyn_sched(call.tail.sched, call.tail.sched_len, 1 + (long long)grid.y * grid.z);
+  const hipStream_t s = call.tail.stream;
   switch (c.cc) {
     case 8: return x3_launch_cc<8>(c.nw, c.wm, wn, in_op, post_op, a, grid, lds, s);
     case 16: return x3_launch_cc<16>(c.nw, c.wm, wn, in_op, post_op, a, grid, lds, s);
@@ -963,22 +966,20 @@ int fvc_conv2d_nhwc_x3_tap(const float* x, const void* wpack, float osc, const f
                            float* P, int batch, int h, int w, int cin, int cout, int ksize, int stride, int act,
                            const void* tap_wpack, float tap_osc, int pcp, int cu_reserve, int* overflow_flag,
                            int* sched, int sched_len, fvc_stream_t stream) {
-  if (cu_reserve < 0 || sched_len < 0 || !tap_wpack || !fvc_conv_x3_tap_supported(cin, cout, ksize, stride, 0, pcp))
-    return FVC_EINVAL;
-  return run_x3(x, wpack, osc, bias, res, P, batch, h, w, cin, cout, ksize, stride, 0, FVC_IN_NONE, act,
-                FVC_POST_NONE, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream, tap_wpack, tap_osc,
-                pcp);
+  if (!tap_wpack || !fvc_conv_x3_tap_supported(cin, cout, ksize, stride, 0, pcp)) return FVC_EINVAL;
+  FvcConvCall c{x, wpack, osc, bias, res, P, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.act = act; c.tw = tap_wpack; c.tosc = tap_osc; c.pcp = pcp;
+  return run_x3({cin, cout, ksize, stride, 0}, c);
 }
 
 int fvc_deconv2d_nhwc_x3_tap(const float* x, const void* wpack, float osc, const float* bias, const float* res,
                              float* P, int batch, int h, int w, int cin, int cout, int ksize, int stride, int act,
                              const void* tap_wpack, float tap_osc, int pcp, int cu_reserve, int* overflow_flag,
                              int* sched, int sched_len, fvc_stream_t stream) {
-  if (cu_reserve < 0 || sched_len < 0 || !tap_wpack || !fvc_conv_x3_tap_supported(cin, cout, ksize, stride, 1, pcp))
-    return FVC_EINVAL;
-  return run_x3(x, wpack, osc, bias, res, P, batch, h, w, cin, cout, ksize, stride, 1, FVC_IN_NONE, act,
-                FVC_POST_NONE, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream, tap_wpack, tap_osc,
-                pcp);
+  if (!tap_wpack || !fvc_conv_x3_tap_supported(cin, cout, ksize, stride, 1, pcp)) return FVC_EINVAL;
+  FvcConvCall c{x, wpack, osc, bias, res, P, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.act = act; c.tw = tap_wpack; c.tosc = tap_osc; c.pcp = pcp;
+  return run_x3({cin, cout, ksize, stride, 1}, c);
 }
 
 int fvc_conv_x3_pool_supported(int cin, int cout, int ksize) {
@@ -989,27 +990,28 @@ int fvc_conv_x3_pool_supported(int cin, int cout, int ksize) {
 int fvc_conv2d_nhwc_x3_pool(const float* x, const void* wpack, float osc, const float* bias, const float* res,
                             float* y, float* pool, int batch, int h, int w, int cin, int cout, int ksize, int act,
                             int cu_reserve, int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
-  if (cu_reserve < 0 || sched_len < 0 || !pool || !fvc_conv_x3_pool_supported(cin, cout, ksize)) return FVC_EINVAL;
-  return run_x3(x, wpack, osc, bias, res, y, batch, h, w, cin, cout, ksize, 1, 0, FVC_IN_NONE, act, FVC_POST_NONE,
-                cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream, nullptr, 0.f, 0, pool);
+  if (!pool || !fvc_conv_x3_pool_supported(cin, cout, ksize)) return FVC_EINVAL;
+  FvcConvCall c{x, wpack, osc, bias, res, y, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.act = act; c.pool = pool;
+  return run_x3({cin, cout, ksize, 1, 0}, c);
 }
 
 int fvc_conv2d_nhwc_x3(const float* x, const void* wpack, float osc, const float* bias,
                        const float* res, float* y, int batch, int h, int w, int cin, int cout,
                        int ksize, int stride, int in_op, int act, int post_op, int cu_reserve,
                        int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
-  if (cu_reserve < 0 || sched_len < 0) return FVC_EINVAL;
-  return run_x3(x, wpack, osc, bias, res, y, batch, h, w, cin, cout, ksize, stride, 0, in_op, act,
-                post_op, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream);
+  FvcConvCall c{x, wpack, osc, bias, res, y, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.in_op = in_op; c.act = act; c.post_op = post_op;
+  return run_x3({cin, cout, ksize, stride, 0}, c);
 }
 
 int fvc_deconv2d_nhwc_x3(const float* x, const void* wpack, float osc, const float* bias,
                          const float* res, float* y, int batch, int h, int w, int cin, int cout,
                          int ksize, int stride, int in_op, int act, int post_op, int cu_reserve,
                          int* overflow_flag, int* sched, int sched_len, fvc_stream_t stream) {
-  if (cu_reserve < 0 || sched_len < 0) return FVC_EINVAL;
-  return run_x3(x, wpack, osc, bias, res, y, batch, h, w, cin, cout, ksize, stride, 1, in_op, act,
-                post_op, cu_reserve, overflow_flag, sched, sched_len, (hipStream_t)stream);
+  FvcConvCall c{x, wpack, osc, bias, res, y, batch, h, w, {cu_reserve, overflow_flag, sched, sched_len, stream}};
+  c.in_op = in_op; c.act = act; c.post_op = post_op;
+  return run_x3({cin, cout, ksize, stride, 1}, c);
 }
 
 }  // extern "C"

@@ -549,7 +549,7 @@ bool deal(const int ntaps[4], int ntp, int S, int wm, int wn, int pair, int wt[k
 // Stride-2 transposed convs with 64 / 96 / 128 input and 64 / 128 output channels, when two
 // full-channel tile buffers fit in LDS. FVC_DX=0 keeps them on fvc_conv_x3.hip's kernel (read at
 // pack AND launch: both come through here).
-bool config(const FvcTaps& t, int cinp, int ntp, int frag, int& th, int nks[4], long long wcls[4], long long& wtotal) {
+bool config(const FvcTaps& t, int cinp, int ntp, int frag, Plan& p) {
   if (t.nclass != 4 || t.sout != 2 || !fvc_env_int("FVC_DX", 1) || (cinp != 64 && cinp != 96 && cinp != 128) ||
       (ntp != 2 && ntp != 4))
     return false;
@@ -561,77 +561,59 @@ bool config(const FvcTaps& t, int cinp, int ntp, int frag, int& th, int nks[4], 
   const int R = sw == 16 ? 8 : (ntp == 4 ? 2 : 4);
   const int ir = R + (t.dymax - t.dymin), ic = sw + (t.dxmax - t.dxmin);
   if (maxt > kMaxTaps || lds_bytes(cinp, plane_pix(ir, ic)) > 160 * 1024) return false;
-  th = R;
-  wtotal = 0;
+  p.th = R;
+  p.wtotal = 0;
   for (int cl = 0; cl < 4; ++cl) {
-    nks[cl] = fvc_cdiv(t.ntaps[cl] * (cinp / 8), 2);
-    wcls[cl] = wtotal;
-    wtotal += (long long)nks[cl] * ntp * frag;
+    p.nks[cl] = fvc_cdiv(t.ntaps[cl] * (cinp / 8), 2);
+    p.wcls[cl] = p.wtotal;
+    p.wtotal += (long long)p.nks[cl] * ntp * frag;
   }
   return true;
 }
 
 // R input rows x 32 columns per work item, the item's wave-tiles dealt to the 8 waves (deal()).
 // Tap form: one strip x all 4 N-tiles per wave-tile.
-int run(const FvcTaps& t, int cinp, int coutp, int ntp, int th, const int nks[4], const long long wcls[4],
-        const float* x, const void* wpack, float osc, const float* bias, const float* res, float* y, int batch, int h,
-        int w, int cout, int in_op, int act, int post_op, int cu_reserve, int* ovf, int* sched, int sched_len,
-        hipStream_t s, const void* tw, float tosc, int pcp, unsigned y_bytes, unsigned x_bytes) {
-  const bool tap = tw != nullptr;
-  if (tap && res) return FVC_EINVAL;
-  const int R = th;
+int run(const FvcTaps& t, int cinp, int coutp, int ntp, int cout, const Plan& p, const FvcConvCall& c,
+        unsigned y_bytes, unsigned x_bytes) {
+  const bool tap = c.tw != nullptr;
+  if (tap && c.res) return FVC_EINVAL;
+  const int R = p.th;
   const int sw = strip_width(cinp);
   const int S = R / (32 / sw);  // strips per item
   const int wm = tap ? 1 : 2, wn = tap ? ntp : 2;
   DxArgs d;
-  d.x = x;
-  d.w = (const uint4*)wpack;
-  d.bias = bias;
-  d.res = res;
-  d.y = y;
-  d.post_exp = post_op == FVC_POST_EXP ? 1 : 0;
-  d.B = batch;
-  d.H = h;
-  d.W = w;
-  d.cout = cout;
-  d.coutp = coutp;
-  d.ntp = ntp;
-  d.R = R;
-  d.sw = sw;
+  d.x = c.x; d.w = (const uint4*)c.wpack; d.bias = c.bias; d.res = c.res; d.y = c.y;
+  d.post_exp = c.post_op == FVC_POST_EXP ? 1 : 0;
+  d.B = c.batch; d.H = c.h; d.W = c.w;
+  d.cout = cout; d.coutp = coutp; d.ntp = ntp;
+  d.R = R; d.sw = sw;
   d.ir = R + (t.dymax - t.dymin);
   d.ic = sw + (t.dxmax - t.dxmin);
   d.ps = plane_pix(d.ir, d.ic);
-  d.dymin = t.dymin;
-  d.dxmin = t.dxmin;
+  d.dymin = t.dymin; d.dxmin = t.dxmin;
   d.inv_ic = 1.0f / (float)d.ic;
-  d.tiles_x = fvc_cdiv(w, sw);
-  d.tiles_y = fvc_cdiv(h, R);
-  const long long nitems = (long long)batch * d.tiles_x * d.tiles_y;
+  d.tiles_x = fvc_cdiv(c.w, sw);
+  d.tiles_y = fvc_cdiv(c.h, R);
+  const long long nitems = (long long)c.batch * d.tiles_x * d.tiles_y;
   if (nitems >= (1LL << 30)) return FVC_EINVAL;
   d.nitems = (int)nitems;
-  d.osc = osc;
-  d.osc_c = fvc_lo_scale(osc);
-  d.act_slope = fvc_act_slope(act);
+  d.osc = c.osc; d.osc_c = fvc_lo_scale(c.osc); d.act_slope = fvc_act_slope(c.act);
   for (int cl = 0; cl < 4; ++cl) {
-    d.nks[cl] = nks[cl];
+    d.nks[cl] = p.nks[cl];
     d.oy0[cl] = t.oy0[cl];
     d.ox0[cl] = t.ox0[cl];
-    d.wcls[cl] = wcls[cl];
+    d.wcls[cl] = p.wcls[cl];
     for (int i = 0; i <= kMaxTaps; ++i)
       d.toff[cl][i] = i < t.ntaps[cl] ? (t.tdy[cl][i] - t.dymin) * d.ic + (t.tdx[cl][i] - t.dxmin) : 0;
   }
   if (!deal(t.ntaps, ntp, S, wm, wn, fvc_env_int("FVC_DX_PAIR", -1), d.wt)) return FVC_EINVAL;
-  d.y_bytes = y_bytes;
-  d.x_bytes = x_bytes;
-  d.ovf = ovf;
-  d.tw = (const uint4*)tw;
-  d.tosc = tosc;
-  d.tosc_c = fvc_lo_scale(tosc);
-  d.pcp = pcp;
-  const int ncu = fvc_persistent_cus(cu_reserve);
+  d.y_bytes = y_bytes; d.x_bytes = x_bytes;
+  d.ovf = c.tail.ovf;
+  d.tw = (const uint4*)c.tw; d.tosc = c.tosc; d.tosc_c = fvc_lo_scale(c.tosc); d.pcp = c.pcp;
+  const int ncu = fvc_persistent_cus(c.tail.cu_reserve);
   const int grid = ncu < d.nitems ? ncu : d.nitems;
-  d.sched = fvc_dyn_sched(sched, sched_len, 2);
-  return launch(d, cinp, wm, wn, in_op, tap, grid, lds_bytes(cinp, d.ps), s);
+  d.sched = fvc_dyn_sched(c.tail.sched, c.tail.sched_len, 2);
+  return launch(d, cinp, wm, wn, c.in_op, tap, grid, lds_bytes(cinp, d.ps), c.tail.stream);
 }
 
 }  // namespace fvc_dx

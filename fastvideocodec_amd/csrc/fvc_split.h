@@ -164,6 +164,36 @@ static inline int* fvc_dyn_sched(int* sched, long long sched_len, long long need
   return (sched && sched_len >= need && fvc_env_int("FVC_X3_DYN", 1)) ? sched : nullptr;
 }
 
+// The launch tail every persistent split-precision entry point ends with (kernels._launch_tail):
+// CUs left to other streams, the overflow flag, the schedule scratch with its length, the stream.
+struct FvcTail {
+  int cu_reserve;
+  int *ovf, *sched;
+  int sched_len;
+  hipStream_t stream;
+};
+static inline bool fvc_tail_ok(const FvcTail& t) { return t.cu_reserve >= 0 && t.sched_len >= 0; }
+
+// One launch of a split-precision conv family. An entry point lists the members up to `tail` in
+// the order of its own C ABI arguments and names what else it sets: the ops, and the optional
+// fused parts, absent by default.
+struct FvcConvCall {
+  const float* x;
+  const void* wpack;
+  float osc;
+  const float *bias, *res;
+  float* y;  // the output, or the tap partials P [batch][Ho][Wo][pcp] when tw is set
+  int batch, h, w;
+  FvcTail tail;
+  int in_op = FVC_IN_NONE, act = FVC_ACT_NONE, post_op = FVC_POST_NONE;
+  const void* tw = nullptr;  // tap epilogue: packed partial weights, their scale, channels of P
+  float tosc = 0.f;
+  int pcp = 0;
+  float* pool = nullptr;  // avg_pool2d(y, 2) as a second output
+};
+
+struct FvcConvGeom { int cin, cout, ksize, stride, transposed; };  // the layer a call runs
+
 // kw with max_abs * 2^kw in [2^13, 2^14), clamped to +-100; 0 for an all-zero or non-finite layer
 static inline int fvc_split_kw(double max_abs) {
   if (!(max_abs > 0.0) || !isfinite(max_abs)) return 0;

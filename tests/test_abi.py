@@ -152,6 +152,63 @@ def test_x3_rejects_unsupported_layers():
     assert lib.fvc_conv_x3_supported(64, 3, 3, 1, 0) == 1   # 3x3 cout <= 4: N padded to one MFMA tile
 
 
+# The persistent split-precision conv entry points, arguments in ABI order with values a launch
+# would take; every pointer is one dummy host buffer, which argument validation never dereferences.
+_BUF = np.zeros(16, dtype=np.float32)
+_P = _BUF.ctypes.data
+_TAIL = dict(cu_reserve=0, overflow_flag=_P, sched=_P, sched_len=4, stream=None)
+_IMG = dict(batch=1, h=8, w=8)
+_X3 = dict(x=_P, wpack=_P, osc=1.0, bias=_P, res=None, y=_P, **_IMG, cin=64, cout=64, ksize=3, stride=1,
+           in_op=0, act=0, post_op=0, **_TAIL)
+_ENTRY = {
+    "x3": ("fvc_conv2d_nhwc_x3", _X3),
+    "deconv_x3": ("fvc_deconv2d_nhwc_x3", dict(_X3, cin=128, cout=128, stride=2)),
+    "x3_pool": ("fvc_conv2d_nhwc_x3_pool", dict(x=_P, wpack=_P, osc=1.0, bias=_P, res=None, y=_P, pool=_P, **_IMG,
+                                                cin=64, cout=64, ksize=3, act=0, **_TAIL)),
+    "x3_tap": ("fvc_conv2d_nhwc_x3_tap", dict(x=_P, wpack=_P, osc=1.0, bias=_P, res=None, P=_P, **_IMG, cin=64, cout=64,
+                                              ksize=3, stride=1, act=0, tap_wpack=_P, tap_osc=1.0, pcp=28, **_TAIL)),
+    "wino": ("fvc_conv2d_nhwc_wino", dict(x=_P, wpack=_P, osc=1.0, bias=_P, res=None, y=_P, pool=None, **_IMG,
+                                          in_op=0, act=0, **_TAIL)),
+    "wino_tap": ("fvc_conv2d_nhwc_wino_tap", dict(x=_P, wpack=_P, osc=1.0, bias=_P, res=None, P=_P, **_IMG, act=0,
+                                                  tap_wpack=_P, tap_osc=1.0, pcp=28, **_TAIL)),
+    "wino_up": ("fvc_conv2d_nhwc_wino_up", dict(skip=_P, low=_P, xsum=_P, wpack=_P, osc=1.0, bias=_P, y=_P, **_IMG,
+                                                in_op=0, act=0, **_TAIL)),
+    "wino128": ("fvc_conv2d_nhwc_wino128", dict(x=_P, wpack=_P, osc4=_P, bias=_P, y=_P, **_IMG, in_op=0, act=0,
+                                                **_TAIL)),
+    "wr7": ("fvc_conv2d_nhwc_wr7", dict(x=_P, xp=32, upack=_P, nt=2, osc=1.0, bias=_P, y=_P, yp=32, **_IMG, mode=0,
+                                        act=0, **_TAIL)),
+}
+# (entry point, the one bad argument): read off the validation code of the four families
+_REJECTED = (
+    [(e, bad) for e in ("x3", "deconv_x3", "x3_pool", "x3_tap", "wino", "wr7")
+     for bad in (dict(cu_reserve=-1), dict(sched_len=-1))] +
+    [("x3", dict(x=None)), ("x3", dict(wpack=None)), ("x3", dict(y=None)), ("x3", dict(batch=0)),
+     ("x3_tap", dict(tap_wpack=None)), ("x3_tap", dict(pcp=36)), ("x3_tap", dict(pcp=6)),
+     ("x3_tap", dict(cout=96)),                 # three N-tiles: no wave holds every output channel
+     ("x3_pool", dict(pool=None)),
+     ("x3_pool", dict(cin=128, cout=128)),      # four N-tiles: two N-groups
+     ("wino", dict(in_op=2)),                   # FVC_IN_ABS: the Winograd staging has none / ReLU only
+     ("wino", dict(act=7)),
+     ("wino_tap", dict(pcp=0)),
+     ("wino_up", dict(h=7)), ("wino_up", dict(low=None)),
+     ("wino128", dict(osc4=None)),
+     ("wr7", dict(mode=3)), ("wr7", dict(nt=3)), ("wr7", dict(bias=None))])  # mode 0 needs its bias
+
+
+@pytest.mark.parametrize("entry,bad", _REJECTED, ids=lambda v: v if isinstance(v, str) else
+                         ",".join(f"{k}={x}" for k, x in v.items()))
+def test_conv_entry_points_reject_bad_arguments(entry, bad):
+    """One bad argument each: the entry point returns FVC_EINVAL from its argument validation, before
+    anything is launched (so no GPU is needed and the dummy pointers are never read)."""
+    lib = _lib.load()
+    assert lib.fvc_conv_x3_tap_supported(64, 64, 3, 1, 0, 28) == 1 and lib.fvc_conv_x3_pool_supported(64, 64, 3) == 1
+    name, good = _ENTRY[entry]
+    assert set(bad) <= set(good)
+    args = dict(good, **bad)
+    assert len(args) == len(_lib._SIGS[name][1])
+    assert getattr(lib, name)(*args.values()) == -1000  # FVC_EINVAL
+
+
 def test_checkpoint_loading_semantics(tmp_path, seeded_sd):
     """DVC/net.py:21-34 load_model: unknown keys are dropped, a missing file raises; seeded
     weights are flagged."""

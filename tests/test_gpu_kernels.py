@@ -281,6 +281,38 @@ def test_conv_x3_batch_split(dev, with_res, monkeypatch):
     assert torch.equal(y1, y2)
 
 
+# (producer cin, cout, stride, transposed, with_res, consumer cout, H, W): 3x3 producers and consumers
+TAP_SPLIT_CASES = [(64, 64, 1, False, True, 3, 20, 40),     # direct kernel (FVC_WINO=0), P of 28 channels
+                   (128, 128, 2, True, False, 2, 8, 8)]     # all-classes kernel, P of 20 channels
+
+
+@pytest.mark.parametrize("case", TAP_SPLIT_CASES, ids=["direct", "all-classes"])
+def test_conv_x3_tap_batch_split(dev, case, monkeypatch):
+    """The batch split of both tap forms: P advances by pcp channels per pixel, the residual by the
+    producer's 64. B = 3 split into 1 + (1 + 1) images must give the bits of the unsplit launch.
+    The split point is one image plus 4 bytes of the larger of P and the residual: run_x3 splits on
+    either tensor and refuses a single image at or over the limit (with one image of P plus 4, the
+    64-channel residual of the direct case is refused, FVC_EINVAL, before anything is launched)."""
+    ci, co, s, tr, with_res, c2, H, W = case
+    monkeypatch.setenv("FVC_WINO", "0")  # read when the producer is packed
+    g = torch.Generator().manual_seed(ci + c2)
+    x = to_nhwc(torch.randn(3, ci, H, W, generator=g)).to(dev)
+    w1 = torch.randn((ci, co, 3, 3) if tr else (co, ci, 3, 3), generator=g) * (1.0 / (ci * 9) ** 0.5)
+    w2 = torch.randn(c2, co, 3, 3, generator=g) * (1.0 / (co * 9) ** 0.5)
+    pc = K.PackedConv(w1, torch.randn(co, generator=g) * 0.1, 3, s, tr, dev, precision="x3")
+    tap = K.TapConsumer(w2, torch.zeros(c2), 3, 1, False, dev)
+    assert tap.pcp == K.cp4(9 * c2) and pc.tap_fusable(tap) and not pc.wino and pc.dx == tr
+    ho, wo = pc.out_hw(H, W)
+    res = to_nhwc(torch.randn(3, co, ho, wo, generator=g)).to(dev) if with_res else None
+    p_image, res_image = ho * wo * tap.pcp * 4, ho * wo * co * 4 if with_res else 0
+    P1 = pc.call_tap(x, tap, act=K.ACT_LRELU, res=res)
+    monkeypatch.setenv("FVC_X3_SPLIT_BYTES", str(max(p_image, res_image) + 4))
+    assert K.x3_dispatches(3, p_image, res_image) == 3
+    P2 = pc.call_tap(x, tap, act=K.ACT_LRELU, res=res)
+    torch.cuda.synchronize()
+    assert torch.equal(P1, P2)
+
+
 def test_conv_x3_overflow_flag(dev):
     """|activation| >= 65000 cannot be split into fp16 halves: the x3 kernel must flag it."""
     w = torch.randn(64, 64, 3, 3) * 0.05
