@@ -1,9 +1,16 @@
-"""Command line: python -m fastvideocodec_amd encode | decode | info.
+"""Command line: python -m fastvideocodec_amd encode | decode | verify | info.
 
   encode IN.y4m|IN.yuv OUT.fvc [--size WxH] [--gop N] [--level L] [--checkpoint PATH]
-         [--matrix bt601|bt709] [--range limited|full] [--batch G]     prints one JSON line of stats
-  decode IN.fvc OUT.y4m                                                prints one JSON line
+         [--matrix bt601|bt709] [--range limited|full] [--batch G]
+         [--digest] [--self-check]                                     prints one JSON line of stats
+  decode IN.fvc OUT.y4m [--checkpoint PATH] [--no-verify]              prints one JSON line
+  verify IN.fvc [--checkpoint PATH]                                    decodes without writing; one JSON line
   info   IN.fvc                                                        header and record counts (no GPU)
+
+--digest stamps every record with a digest of the encoder's reconstruction; decode checks each frame
+against it unless --no-verify, and fails at the first frame that differs. --self-check makes the
+encoder decode the bytes it has just serialised and compare (the file does not change).
+verify exits 0 when every frame matches, 1 at a mismatch, 2 when the file carries no digests.
 """
 from __future__ import annotations
 
@@ -44,10 +51,17 @@ def main(argv=None) -> int:
     e.add_argument("--matrix", choices=("bt601", "bt709"), default="bt709")
     e.add_argument("--range", choices=("limited", "full"), default="limited")
     e.add_argument("--batch", type=int, default=1)
+    e.add_argument("--digest", action="store_true", help="stamp every record with its reconstruction digest")
+    e.add_argument("--self-check", action="store_true",
+                   help="decode every serialised payload and compare its digest with the encoder's")
     d = sub.add_parser("decode", help="FVC1 container -> Y4M")
     d.add_argument("src")
     d.add_argument("dst")
     d.add_argument("--checkpoint", default=None)
+    d.add_argument("--no-verify", action="store_true", help="do not check the frame digests the file carries")
+    v = sub.add_parser("verify", help="decode without writing and check every frame digest")
+    v.add_argument("src")
+    v.add_argument("--checkpoint", default=None)
     i = sub.add_parser("info", help="print a container's header and record counts")
     i.add_argument("src")
     a = ap.parse_args(argv)
@@ -63,7 +77,8 @@ def main(argv=None) -> int:
         model = _model(a.level, a.checkpoint)
         with open_video(a.src, a.size) as reader, open(a.dst, "wb") as f:
             stats = encode_file(model, reader, f, gop=a.gop, batch=a.batch,
-                                pixfmt={"matrix": a.matrix, "range": a.range})
+                                pixfmt={"matrix": a.matrix, "range": a.range}, digest=a.digest,
+                                self_check=a.self_check)
         print(json.dumps(stats, sort_keys=True))
         return 0
     from .container import ContainerReader, display_size
@@ -71,11 +86,28 @@ def main(argv=None) -> int:
     from .video_io import Y4MWriter
     with open(a.src, "rb") as f:
         data = f.read()
-    header = ContainerReader(data).header
+    reader = ContainerReader(data)
+    header = reader.header
+    if a.cmd == "verify":
+        from .digest import DigestMismatch
+        order = [(e[1], e[2], e[3]) for vg in reader.gops() for e in reader.gop_records(*vg)]
+        if header.get("frame_digest") is None:
+            print(json.dumps({"frames": len(order), "verified": 0, "first_mismatch": None}, sort_keys=True))
+            return 2
+        model = _model(header["level"], a.checkpoint)
+        try:
+            stats = decode_file(model, data, None)
+            res = {"frames": stats["frames"], "verified": stats["verified"], "first_mismatch": None}
+        except DigestMismatch as m:
+            print(m, file=sys.stderr)
+            at = order.index((m.view, m.gop, m.frame))  # frames decoded and verified before it
+            res = {"frames": at, "verified": at, "first_mismatch": [m.view, m.gop, m.frame]}
+        print(json.dumps(res, sort_keys=True))
+        return 0 if res["first_mismatch"] is None else 1
     h, w = display_size(header)
     model = _model(header["level"], a.checkpoint)
     with Y4MWriter(a.dst, w, h, fps=header.get("fps", (25, 1))) as writer:
-        stats = decode_file(model, data, writer)
+        stats = decode_file(model, data, writer, verify=not a.no_verify)
     print(json.dumps(stats, sort_keys=True))
     return 0
 

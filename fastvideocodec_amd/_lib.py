@@ -115,6 +115,7 @@ _SIGS = {
     "fvc_yuv420_to_rgb_pad": (c_int, [vp, vp, vp, vp] + [c_int] * 7 + [vp]),
     "fvc_rgb_to_yuv420_crop": (c_int, [vp, vp, vp, vp] + [c_int] * 7 + [vp]),
     "fvc_sse_u8": (c_int, [vp, vp, c_size_t, vp, vp]),
+    "fvc_frame_digest_f32": (c_int, [vp, c_int, c_size_t, vp, vp]),
 }
 
 EXPORTED = tuple(_SIGS)

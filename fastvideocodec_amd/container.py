@@ -19,6 +19,11 @@ The header carries the codec name / level, frame geometry, GOP length, view and 
 I-frame transform parameters and a CRC-32 of every entropy table, which a reader checks against
 its own model before decoding. height / width are the coded (padded) size; a file coded from 8-bit
 YUV (transcode.py) also carries display_height / display_width, pixfmt, fps and frames (make_header).
+
+A file whose header has "frame_digest": "splitmix64-f32" carries, as the last 8 bytes (u64) of every
+record payload, the digest (digest.py) of that frame's reconstruction at the coded size: what the
+encoder held as its reference, and what a decoder must reproduce. The payload parsers read by
+position and ignore trailing bytes, so a reader that knows nothing of the key decodes such a file.
 """
 from __future__ import annotations
 
@@ -30,6 +35,7 @@ import zlib
 import numpy as np
 import torch
 
+from . import digest as DG
 from . import iframe as IF
 from .entropy_models import EncodedStreams
 from .net import FRAMINGS, PFrameBitstream
@@ -126,25 +132,32 @@ class ContainerWriter:
     def __init__(self, f, header: dict):
         self.f = f
         self.index = []
+        self.digests = _has_digests(header)
         hb = json.dumps(header, sort_keys=True).encode()
         f.write(MAGIC + struct.pack("<HI", VERSION, len(hb)) + hb)
 
-    def _record(self, kind, view, gop, frame, payload):
+    def _record(self, kind, view, gop, frame, payload, digest=None):
+        if (digest is not None) != self.digests:
+            raise ValueError("every record of a file carries a digest, or none does (header key frame_digest)")
+        if digest is not None:
+            payload = payload + struct.pack("<Q", int(digest) & DG.MASK)
         self.index.append((kind, view, gop, frame, self.f.tell()))
         self.f.write(_REC.pack(kind, view, gop, frame, len(payload)))
         self.f.write(payload)
 
-    def write_iframe(self, view, gop, frame, bs: IF.IFrameBitstream):
-        self._record(b"I", view, gop, frame, iframe_payload(bs))
+    def write_iframe(self, view, gop, frame, bs: IF.IFrameBitstream, digest: int | None = None):
+        self._record(b"I", view, gop, frame, iframe_payload(bs), digest)
 
-    def write_pframe(self, view, gop, frame, payload: bytes):
-        self._record(b"P", view, gop, frame, payload)
+    def write_pframe(self, view, gop, frame, payload: bytes, digest: int | None = None):
+        self._record(b"P", view, gop, frame, payload, digest)
 
-    def write_payload(self, kind: bytes, view, gop, frame, payload: bytes):
-        """A record whose payload (iframe_payload / pframe_payload) was serialised earlier."""
+    def write_payload(self, kind: bytes, view, gop, frame, payload: bytes, digest: int | None = None):
+        """A record whose payload (iframe_payload / pframe_payload) was serialised earlier. digest
+        (the frame's reconstruction digest, given exactly when the header has the frame_digest key)
+        is appended to it."""
         if kind not in (b"I", b"P"):
             raise ValueError(f"unknown record kind {kind!r}")
-        self._record(kind, view, gop, frame, payload)
+        self._record(kind, view, gop, frame, payload, digest)
 
     def close(self):
         pos = self.f.tell()
@@ -184,11 +197,30 @@ class ContainerReader:
         return sorted({(e[1], e[2]) for e in self.index})
 
 
-def make_header(model, height, width, gop, gops, framing, q, display=None, pixfmt=None, fps=None, frames=None):
+def _has_digests(header) -> bool:
+    name = header.get("frame_digest")
+    if name is not None and name != DG.NAME:
+        raise ValueError(f"unknown frame digest {name!r} (this reader knows {DG.NAME!r})")
+    return name is not None
+
+
+def record_digest(header, payload) -> int | None:
+    """The reconstruction digest a record payload carries (its last 8 bytes), or None for a file
+    whose header does not announce digests."""
+    if not _has_digests(header):
+        return None
+    if len(payload) < 8:
+        raise ValueError("record payload too short to carry a digest")
+    return struct.unpack_from("<Q", payload, len(payload) - 8)[0]
+
+
+def make_header(model, height, width, gop, gops, framing, q, display=None, pixfmt=None, fps=None, frames=None,
+                frame_digest=False):
     """The container header. height / width are the coded (padded) size. Optional keys, absent
     from a file of float RGB frames at the coded size: display = (h, w) -> display_height /
     display_width (what a decoder crops to), pixfmt = {"chroma": "420", "matrix", "range"} (the
-    source's 8-bit format, which a decoder converts back to), fps = (num, den), frames (total)."""
+    source's 8-bit format, which a decoder converts back to), fps = (num, den), frames (total).
+    frame_digest=True announces a reconstruction digest at the end of every record payload."""
     header = {"codec": model.name, "level": model.compression_level, "height": height, "width": width, "gop": gop,
               "gops": gops, "tables_crc32": tables_crc(model), "framing": framing,
               "iframe": {"transform": "rct+legall53", "levels": IF.LEVELS, "block": IF.BLOCK,
@@ -201,6 +233,8 @@ def make_header(model, height, width, gop, gops, framing, q, display=None, pixfm
         header["fps"] = [int(fps[0]), int(fps[1])]
     if frames is not None:
         header["frames"] = int(frames)
+    if frame_digest:
+        header["frame_digest"] = DG.NAME
     return header
 
 
@@ -223,38 +257,56 @@ def info(data: bytes) -> dict:
             "pframes": kinds.count(b"P"), "bytes": len(r.data)}
 
 
-def encode_video(model, video: torch.Tensor, f, iframe_q=None, framing="segment", views=None):
+def check_gop_digests(view, gop, expected, got):
+    """Compare one GOP's stored digests [(frame, uint64)] with the decoded frames' (device int64
+    [1] each): one host read, DigestMismatch at the first differing frame."""
+    if not expected:
+        return
+    have = torch.cat(got).cpu().tolist()
+    for (frame, want), g in zip(expected, have):
+        if want != DG.to_uint64(g):
+            raise DG.DigestMismatch(view, gop, frame, want, g)
+
+
+def encode_video(model, video: torch.Tensor, f, iframe_q=None, framing="segment", views=None, digest=False):
     """Encode video [N, T, 3, H, W] (N GOPs, H and W multiples of 64) into container file f.
     GOP n is muxed as (view = views[n] if given else 0, gop = n). Frame 0 of each GOP is coded by
     the I-frame codec (step iframe_q, default from model.I_level: iframe.iframe_step), frames
     1..T-1 by the P-frame codec against the encoder's own previous reconstruction (what the
-    decoder will hold). Returns the encoder's reconstructions [N, T, 3, H, W]."""
+    decoder will hold). digest=True stamps every record with the digest of its reconstruction, which
+    decode_video checks. Returns the encoder's reconstructions [N, T, 3, H, W]."""
     N, T, C, H, W = video.shape
     q = IF.iframe_step(model.I_level) if iframe_q is None else int(iframe_q)
-    w = ContainerWriter(f, make_header(model, H, W, T, N, framing, q))
+    w = ContainerWriter(f, make_header(model, H, W, T, N, framing, q, frame_digest=digest))
+    stamp = (lambda x: DG.to_uint64(DG.frame_digest(x).item())) if digest else (lambda x: None)
     recons = torch.empty_like(video)
     for n in range(N):
         v = 0 if views is None else int(views[n])
         ibs, x = IF.encode(video[n, 0:1].contiguous(), q)
-        w.write_iframe(v, n, 0, ibs)
+        w.write_iframe(v, n, 0, ibs, stamp(x))
         recons[n, 0] = x[0]
         for t in range(1, T):
             bs, x = model.compress(video[n, t:t + 1].contiguous(), x, framing=framing)
-            w.write_pframe(v, n, t, pframe_payload(bs))
+            w.write_pframe(v, n, t, pframe_payload(bs), stamp(x))
             recons[n, t] = x[0]
     w.close()
     return recons
 
 
-def decode_video(model, data: bytes, device=None):
-    """Decode every GOP of a container: {(view, gop): frames [T, 3, H, W]} on the device."""
+def decode_video(model, data: bytes, device=None, verify=True):
+    """Decode every GOP of a container: {(view, gop): frames [T, 3, H, W]} on the device. When the
+    file carries frame digests, every decoded frame's digest is computed on the device and compared
+    once per GOP (one host read per GOP); DigestMismatch names the first differing frame.
+    verify=False skips the check."""
     r = ContainerReader(data)
     if r.header.get("tables_crc32") != tables_crc(model):
         raise ValueError("container was coded with different entropy tables (model weights differ)")
     dev = torch.device(device) if device is not None else next(model.parameters()).device
+    check = verify and _has_digests(r.header)
     out = {}
     for view, gop in r.gops():
         frames = []
+        expected, got = [], []
         x = None
         for e in r.gop_records(view, gop):
             payload = r.record(e)
@@ -263,6 +315,10 @@ def decode_video(model, data: bytes, device=None):
             else:
                 x = model.decompress(pframe_from_payload(payload, dev), x)
             frames.append(x[0])
+            if check:
+                expected.append((e[3], record_digest(r.header, payload)))
+                got.append(DG.frame_digest(x))
+        check_gop_digests(view, gop, expected, got)
         out[(view, gop)] = torch.stack(frames)
     return out
 

@@ -452,6 +452,18 @@ int fvc_rgb_to_yuv420_crop(const float* x, uint8_t* y, uint8_t* u, uint8_t* v, i
                            int wp, int matrix, int range, fvc_stream_t stream);
 int fvc_sse_u8(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* out, fvc_stream_t stream);
 
+/* ------------------------------------------------------------------ per-frame reconstruction digest
+ * x: [batch][n] float32 on the device, read as 32-bit words w (the float bit patterns); out: [batch]
+ * device uint64, zeroed by the call (stream-ordered; the call never waits on the host). Frame b gets
+ *   D = sum_{i < n} mix( ((uint64)i << 32 | w[i]) + 0x9e3779b97f4a7c15 )              mod 2^64
+ *   mix(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31
+ * (the splitmix64 finaliser; all arithmetic mod 2^64) with i counted inside its own frame, so a
+ * frame's digest does not depend on its place in a batch. Position-dependent, and a sum of integers
+ * added with integer atomics: exact and independent of the order of addition. Any 4-byte aligned
+ * base and any n are exact (16-byte loads over each frame's aligned body, single words for the rest).
+ * FVC_EINVAL before any launch: a null pointer, batch <= 0 or > 65535, n == 0, n >= 2^32. */
+int fvc_frame_digest_f32(const float* x, int batch, size_t n, uint64_t* out, fvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
