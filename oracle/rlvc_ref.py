@@ -34,16 +34,23 @@ def gdn_cai(sd, prefix, x, inverse):
     return x * torch.sqrt(norm) if inverse else x * torch.rsqrt(norm)
 
 
-def conv_lstm(sd, prefix, x, state, forget_bias=1.0):
-    C = x.shape[1]
-    c, h = torch.split(state, C, dim=1)
-    y = F.conv2d(torch.cat((x, h), 1), sd[f"{prefix}.conv.weight"], sd[f"{prefix}.conv.bias"], 1, 1)
-    j, i, f, o = torch.split(y, C, dim=1)
+def lstm_gates(j, i, f, o, c, forget_bias=1.0):
+    """ConvLSTM's gate arithmetic (entropy_models.py:367-378) on the conv's four outputs and the
+    previous cell: -> (new cell, before its relu; new hidden)."""
     f = torch.sigmoid(f + forget_bias)
     i = torch.sigmoid(i)
     c = c * f + i * F.relu(j)
     o = torch.sigmoid(o)
     h = o * F.relu(c)
+    return c, h
+
+
+def conv_lstm(sd, prefix, x, state, forget_bias=1.0):
+    C = x.shape[1]
+    c, h = torch.split(state, C, dim=1)
+    y = F.conv2d(torch.cat((x, h), 1), sd[f"{prefix}.conv.weight"], sd[f"{prefix}.conv.bias"], 1, 1)
+    j, i, f, o = torch.split(y, C, dim=1)
+    c, h = lstm_gates(j, i, f, o, c, forget_bias)
     return h, torch.cat((c, h), 1)
 
 
