@@ -116,6 +116,9 @@ _SIGS = {
     "fvc_rgb_to_yuv420_crop": (c_int, [vp, vp, vp, vp] + [c_int] * 7 + [vp]),
     "fvc_sse_u8": (c_int, [vp, vp, c_size_t, vp, vp]),
     "fvc_frame_digest_f32": (c_int, [vp, c_int, c_size_t, vp, vp]),
+    "fvc_ms_ssim_window": (c_int, [vp]),
+    "fvc_ms_ssim_workspace_bytes": (c_size_t, [c_int] * 4),
+    "fvc_ms_ssim_planes": (c_int, [vp, vp] + [c_int] * 5 + [ctypes.c_double, vp, c_size_t, vp, vp]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = ["fvc_conv.hip", "fvc_conv_x3.hip", "fvc_deconv_x3.hip", "fvc_conv_wino.hip", "fvc_conv_wr7.hip", "fvc_conv_stem.hip", "fvc_elem.hip", "fvc_gdn.hip", "fvc_tap_gather.hip", "fvc_coder.hip",
-        "fvc_iframe.hip", "fvc_torchac.hip", "fvc_pixfmt.hip", "fvc_digest.hip"]
+        "fvc_iframe.hip", "fvc_torchac.hip", "fvc_pixfmt.hip", "fvc_digest.hip", "fvc_msssim.hip"]
 # per-source flags: the Winograd transforms stay scalar f32 (packed f32 VALU issues slower beside MFMAs)
 SRC_FLAGS = {"fvc_conv_wino.hip": ["-fno-slp-vectorize"], "fvc_conv_wr7.hip": ["-fno-slp-vectorize"]}
 OUT = os.path.join(HERE, "libfvc.so")

@@ -117,6 +117,22 @@ def PSNR(Y1_raw, Y1_com, use_list=False):
     return out
 
 
+def MSSSIM(Y1_raw, Y1_com, use_list=False):
+    """models.py:475-487: -10*ln(1 - q)/ln(10) of the MS-SSIM q (metrics.ms_ssim), one scalar, or
+    a list with one entry per frame. As there, the metric is called with its package default
+    data_range=255 on frames that hold [0,1] values, and without use_list q is the mean over the
+    batch: a quirk of the reference (C1 and C2 then swamp the statistics and q sits close to 1), kept
+    because it is the number its users compare against. metrics.ms_ssim(x, y, data_range=1.0) is the
+    measure proper."""
+    from . import metrics as MT
+    Y1_com = Y1_com.to(Y1_raw.device)
+    log10 = math.log(10.0)
+    q = MT.ms_ssim(Y1_raw.contiguous(), Y1_com.contiguous(), data_range=255)
+    if not use_list:
+        return -10 * torch.log(1 - q.mean()) / log10
+    return [-10 * torch.log(1 - q[i]) / log10 for i in range(q.numel())]
+
+
 def I_compression(Y1_raw, I_level, model_name="", codec=None):
     """models.py:412-429: code the I-frame, return (Y1_com, bpp, psnr). The reference runs
     bpgenc/bpgdec at quality I_level (binaries absent). codec=None (default): lossless

@@ -20,6 +20,7 @@ import torch
 from . import container as C
 from . import digest as DG
 from . import iframe as IF
+from . import metrics as MT
 from . import pixfmt as PF
 
 DEFAULT_PIXFMT = {"chroma": "420", "matrix": "bt709", "range": "limited"}
@@ -31,7 +32,7 @@ def _upload(frames, dev):
 
 
 def encode_file(model, reader, f, gop=12, framing="segment", iframe_q=None, batch=1, pixfmt=None,
-                recon_writer=None, digest=False, self_check=False):
+                recon_writer=None, digest=False, self_check=False, msssim=False):
     """Code every frame of `reader` (an iterator of (y, u, v) uint8 planes with .width, .height and
     .fps) into container file f. Frame 0 of each GOP of `gop` frames is an I-frame, the rest a
     P-frame chain on the encoder's own reconstruction; the last GOP may be short. pixfmt = {"matrix":
@@ -43,7 +44,11 @@ def encode_file(model, reader, f, gop=12, framing="segment", iframe_q=None, batc
     payload back as soon as it is serialised, decodes it against the decoder-side previous frame and
     compares the digests on the device (one flag read per chunk of gop * batch frames);
     DigestMismatch names the first frame a decoder would not reproduce. The file does not depend
-    on self_check. Returns {"frames", "bytes", "bpp" (over display pixels), "psnr_y",
+    on self_check. msssim=True adds "msssim_y" to the result: per frame the MS-SSIM (metrics.ms_ssim,
+    data range 255) of the 8-bit source Y plane and the Y plane a decoder delivers, at the display
+    size, queued beside the squared errors and read with them; the file does not depend on it, and a
+    display size below five scales' minimum raises before anything is coded.
+    Returns {"frames", "bytes", "bpp" (over display pixels), "psnr_y",
     "psnr_u", "psnr_v" (per frame, reconstruction against source), "height", "width",
     "coded_height", "coded_width", "gops"}."""
     if gop < 1 or batch < 1:
@@ -52,9 +57,12 @@ def encode_file(model, reader, f, gop=12, framing="segment", iframe_q=None, batc
     matrix, yuv_range = pf["matrix"], pf["range"]
     dev = next(model.parameters()).device
     h, w = reader.height, reader.width
+    if msssim and min(h, w) < MT.min_side(5):
+        raise ValueError(f"msssim: a display size of {h}x{w} is too small for five scales: the smaller side is "
+                         f"{min(h, w)}, the minimum is {MT.min_side(5)}")
     q = IF.iframe_step(model.I_level) if iframe_q is None else int(iframe_q)
     records = []   # (kind, gop, frame, payload bytes), in file order
-    sse = []       # device int64 [3] per frame, in file order
+    sse = []       # device int64 [3] per frame, in file order ([4] with msssim: the float64's bits ride along)
     nframes = ngops = 0
     Hp = Wp = None
     frames = iter(reader)
@@ -75,10 +83,11 @@ def encode_file(model, reader, f, gop=12, framing="segment", iframe_q=None, batc
         def finish(i, t, rec, payload, kind):
             k = i * gop + t
             ry, ru, rv = PF.rgb_to_yuv420(rec, h, w, matrix, yuv_range)
-            out[(i, t)] = (kind, payload, torch.cat([PF.sse_u8_device(ry, ys[k:k + 1]),
-                                                      PF.sse_u8_device(ru, us[k:k + 1]),
-                                                      PF.sse_u8_device(rv, vs[k:k + 1])]),
-                           (ry, ru, rv) if recon_writer is not None else None)
+            metric = [PF.sse_u8_device(ry, ys[k:k + 1]), PF.sse_u8_device(ru, us[k:k + 1]),
+                      PF.sse_u8_device(rv, vs[k:k + 1])]
+            if msssim:
+                metric.append(MT.ms_ssim(ys[k:k + 1, None], ry[:, None], data_range=255).view(torch.int64))
+            out[(i, t)] = (kind, payload, torch.cat(metric), (ry, ru, rv) if recon_writer is not None else None)
             if digest or self_check:
                 digs[(i, t)] = DG.frame_digest(rec)
             if self_check:
@@ -136,9 +145,12 @@ def encode_file(model, reader, f, gop=12, framing="segment", iframe_q=None, batc
     s = torch.stack(sse).cpu().numpy()  # the only host wait on the metric
     ch, cwid = PF.chroma_size(h, w)
     psnr = [[PF.psnr_from_sse(int(v), npx) for v in s[:, k]] for k, npx in enumerate((h * w, ch * cwid, ch * cwid))]
-    return {"frames": nframes, "gops": ngops, "bytes": nbytes, "bpp": nbytes * 8.0 / (nframes * h * w),
-            "height": h, "width": w, "coded_height": Hp, "coded_width": Wp,
-            "psnr_y": psnr[0], "psnr_u": psnr[1], "psnr_v": psnr[2]}
+    res = {"frames": nframes, "gops": ngops, "bytes": nbytes, "bpp": nbytes * 8.0 / (nframes * h * w),
+           "height": h, "width": w, "coded_height": Hp, "coded_width": Wp,
+           "psnr_y": psnr[0], "psnr_u": psnr[1], "psnr_v": psnr[2]}
+    if msssim:
+        res["msssim_y"] = np.ascontiguousarray(s[:, 3]).view(np.float64).tolist()
+    return res
 
 
 def decode_file(model, data: bytes, writer, device=None, verify=True):

@@ -464,6 +464,30 @@ int fvc_sse_u8(const uint8_t* a, const uint8_t* b, size_t n, uint64_t* out, fvc_
  * FVC_EINVAL before any launch: a null pointer, batch <= 0 or > 65535, n == 0, n >= 2^32. */
 int fvc_frame_digest_f32(const float* x, int batch, size_t n, uint64_t* out, fvc_stream_t stream);
 
+/* ------------------------------------------------------------------ SSIM / MS-SSIM of planes
+ * x, y: [planes][h][w] on the device, float32 (FVC_DTYPE_F32) or uint8 (FVC_DTYPE_U8), read only.
+ * out: device double [levels][planes][2] = (mean cs, mean ssim) of each plane at each scale, where
+ * with the 11-tap Gaussian window g (sigma 1.5, normalised, taps formed in float32: ms_ssim_window
+ * returns them) applied separably and *valid*, so that the maps are (h-10) x (w-10):
+ *   mu1 = g*x, mu2 = g*y, s1 = g*x^2 - mu1^2, s2 = g*y^2 - mu2^2, s12 = g*xy - mu1 mu2
+ *   cs = (2 s12 + C2) / (s1 + s2 + C2),  ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs
+ *   C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2.
+ * Scale l+1 is scale l averaged over 2x2 windows with a zero row / column in front of an odd side
+ * (side (s+1)/2; window k covers inputs 2k-1 and 2k of an odd side, index -1 is zero, the divisor
+ * is always 4) and is kept as float32 in the workspace. The arithmetic on chip is float64; every
+ * sum is formed in a fixed order without floating-point atomics, so a plane's result is the same
+ * bits in every call and whatever else the batch holds. levels == 1 is plain SSIM. Stream-ordered;
+ * no host wait. ws: 16-byte aligned device memory of at least ms_ssim_workspace_bytes (0 for a
+ * geometry ms_ssim_planes would refuse).
+ * FVC_EINVAL before any launch: a null pointer, an unknown dtype, planes outside 1..65535, levels
+ * outside 1..5, min(h, w) < 11 * 2^(levels-1) (the last scale must hold a window after floor
+ * halving: 176 for five levels), data_range <= 0, a workspace that is too small or misaligned. */
+enum { FVC_DTYPE_F32 = 0, FVC_DTYPE_U8 = 1 };
+int fvc_ms_ssim_window(float* taps11);
+size_t fvc_ms_ssim_workspace_bytes(int planes, int h, int w, int levels);
+int fvc_ms_ssim_planes(const void* x, const void* y, int dtype, int planes, int h, int w, int levels,
+                       double data_range, void* ws, size_t ws_bytes, double* out, fvc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
